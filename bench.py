@@ -25,9 +25,12 @@ exchange, every rank's zone walk is bounded to its share of the free memory, and
 engines, real launches, concurrent walks, the whole launcher / barrier / gather flow; not a measurement.
 PGX_BENCH_FORCE_DIST=1 initialises the process group even for one rank, so that the RCCL path (init with device_id,
 barrier, all_reduce, all_gather on device tensors) runs for real on a 1-GPU box (tests/test_bench_rehearsal_gpu.py).
-Timing: W warm-up steps, then `--windows` windows of EXACTLY K steps each, every window bracketed by barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `value` comes from the MEDIAN window (a single
-20-step window is 2.6 ms of GPU time -- one lucky or unlucky sample), all windows are listed in the line.
+Timing: W warm-up steps, then `--windows` windows (default 1, so that K is the number of timed steps) of EXACTLY K steps
+each, every window bracketed by barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `value`
+and `ms_per_step` come from the MEDIAN window (a single 20-step window is 2.6 ms of GPU time -- one lucky or unlucky
+sample: give a short K more windows), all windows are listed in the line.
+`--dump-outputs DIR`: what the last timed step returned (rank 0's shard), as DIR/<name>.npy -- the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -69,6 +72,46 @@ def algorithmic_bytes_per_agent_step(size: int, agents: int, r: int, obs_bytes: 
     wider action dtypes are budgeted at their real width)."""
     W, P = 2 * r + 1, size + 2 * r
     return 3.0 * obs_bytes * W * W + 3.0 * ((P * P + 7) // 8) / agents + 20.0 + action_bytes
+
+
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files together (64 MB)
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=DUMP_SAMPLE_SEED) -> dict:
+    """--dump-outputs: every array of `arrays` (name -> torch tensor or numpy array, leading axis = environment; None is
+    skipped) as out_dir/<name>.npy in float32.  When they exceed `limit` bytes together, the largest one (the
+    observations) keeps only a fixed, seeded sample of its environments -- which ones is written as <name>_env_index.npy
+    (float64) -- and is cut on the device before it is copied.  -> {name: shape written}"""
+    import numpy as np
+    import torch
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    nbytes = {k: 4 * int(np.prod(v.shape)) for k, v in arrays.items()}  # as float32
+    rows = None
+    limit -= 1024 * (len(arrays) + 1)  # room for the .npy headers
+    if sum(nbytes.values()) > limit:
+        big = max(nbytes, key=nbytes.get)
+        n = arrays[big].shape[0]
+        per_env = nbytes[big] // n
+        keep = (limit - (sum(nbytes.values()) - nbytes[big])) // (per_env + 8)
+        if keep < 1:
+            raise ValueError(f"--dump-outputs: the outputs do not fit in {limit} bytes even with one environment of {big!r}")
+        rows = (big, np.sort(np.random.default_rng(seed).choice(n, keep, replace=False)))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, v in arrays.items():
+        if rows is not None and name == rows[0]:
+            v = v[torch.as_tensor(rows[1], device=v.device)] if isinstance(v, torch.Tensor) else v[rows[1]]
+        if isinstance(v, torch.Tensor):
+            v = v.detach().to(torch.float32).cpu().numpy()
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        written[name] = list(v.shape)
+    if rows is not None:
+        idx = rows[1].astype(np.float64)
+        np.save(os.path.join(out_dir, rows[0] + "_env_index.npy"), idx)
+        written[rows[0] + "_env_index"] = list(idx.shape)
+    return written
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -428,6 +471,9 @@ class EngineStep:
         self.nbuf = 2 if (args.buffers == 0 and args.graph > 0) else args.buffers
         self.graph = None
         self.graph_len = 0
+        self.graph_last = None
+        self.keep_last = False  # --dump-outputs: run() keeps what its last step returned in self.last
+        self.last = None
         self.i = 0
         if args.graph > 0:
             self._capture(args.graph)
@@ -441,18 +487,32 @@ class EngineStep:
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            for k in range(n):
+            for k in range(n - 1):
                 self.env.step(self.pool[k % len(self.pool)], compute_obs=not self.no_obs)
+            # the captured tensors of the graph's last step hold that step's outputs after every replay
+            self.graph_last = self.env.step(self.pool[(n - 1) % len(self.pool)], compute_obs=not self.no_obs)
         self.graph, self.graph_len = g, n
 
     def run(self, steps):
+        self.last = None  # never held into further steps: a held output set changes what the recycler hands out
         if self.graph is not None:
             for _ in range(steps // self.graph_len):
                 self.graph.replay()
+            self.last = self.graph_last if self.keep_last else None
             return
-        for _ in range(steps):
-            self.env.step(self.pool[self.i % len(self.pool)], compute_obs=not self.no_obs)
+        for k in range(steps):
+            if k < steps - 1 or not self.keep_last:
+                self.env.step(self.pool[self.i % len(self.pool)], compute_obs=not self.no_obs)
+            else:
+                self.last = self.env.step(self.pool[self.i % len(self.pool)], compute_obs=not self.no_obs)
             self.i += 1
+
+    def last_outputs(self) -> dict:
+        """The arrays a caller of the timed step() received from the last step of the last run(): observations,
+        rewards, terminated, truncated and the infos' is_active / episode_done / metrics (device tensors)."""
+        obs, rewards, terminated, truncated, infos = self.last
+        return {"obs": obs, "rewards": rewards, "terminated": terminated, "truncated": truncated,
+                "is_active": infos["is_active"], "episode_done": infos["episode_done"], "metrics": infos["metrics"]}
 
     def measure_held_pair(self, steps, windows=3):
         """Secondary figure: the caller keeps step t's outputs alive until step t+1 has returned."""
@@ -906,7 +966,8 @@ def make_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of exactly --steps steps; value = median window")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="timed windows of exactly --steps steps each; value = median window (default 1: --steps timed steps)")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--collision", default="soft", choices=["priority", "block_both", "soft"])
     ap.add_argument("--on-target", default="finish", choices=["finish", "restart", "nothing"])
@@ -940,6 +1001,9 @@ def make_parser():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the secondary figures (two pipelined engines; K-step rollout launches)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step returned as DIR/<name>.npy (float32; at most "
+                         "64 MB in all, the observations cut to a fixed seeded sample of environments when larger)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)  # tests only, see StubStep
     ap.add_argument("--stub-rccl", action="store_true", help=argparse.SUPPRESS)  # tests only: attempt RCCL in stub mode
     return ap
@@ -951,6 +1015,8 @@ def main(argv=None):
         raise SystemExit("--gpus, --steps and --windows must be >= 1")
     if args.graph > 0 and args.steps % args.graph:
         raise SystemExit(f"--steps {args.steps} must be a multiple of --graph {args.graph}")
+    if args.dump_outputs and args.stub:
+        raise SystemExit("--dump-outputs needs the engine: there are no outputs under --stub")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None:
@@ -1042,7 +1108,13 @@ def main(argv=None):
     warm = args.warmup if args.graph <= 0 else -(-args.warmup // args.graph) * args.graph
     if warm:
         step.run(warm)
+    step.keep_last = bool(args.dump_outputs)
     walls, kernel = timed_windows(step, args.windows)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = {"dir": args.dump_outputs, "step": "last timed step", "files": dump_outputs(args.dump_outputs, step.last_outputs())}
+    if args.dump_outputs:
+        step.keep_last, step.last = False, None
     elapsed = statistics.median(walls)
     kernel_ms = statistics.median(kernel)
     per_rank_kernel = [kernel_ms]
@@ -1295,6 +1367,8 @@ def main(argv=None):
                           "are out at any time; `misses` = hand-outs that fell back to fresh torch tensors")
         if extras:
             line["secondary"] = extras
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         line["box"] = fingerprint
         if world == 1 and not args.no_cpu_baseline and not args.stub:
             try:  # the baseline leg must never cost the measured line

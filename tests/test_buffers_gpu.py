@@ -346,12 +346,15 @@ def test_closed_environments_leave_their_buffers_to_the_next_one(monkeypatch):
     """buffers.ParkedBuffers: close() parks the zone-spread observation buffers nobody references any more -- as a WHOLE
     set or not at all --; the next environment with the same observation tensor takes them over without a
     walk (and without new address space); a set the caller still holds a buffer of is NOT parked (the shelf never holds
-    an unclaimable remainder); PGX_POOL_CACHE_MB=0 switches the shelf off; close(release=True) empties it."""
+    an unclaimable remainder); PGX_POOL_CACHE_MB=0 switches the shelf off; close(release=True) empties it.
+    None of torch's own buffers is timed against the pool's here: when one of them wins the candidate timing (a matter of
+    a few per cent on some boxes) no whole zone set exists and there would be nothing to park."""
     import gc as pygc
     import torch
     from pogema_amd import GridConfig, VecPogema, _lib
     from pogema_amd.buffers import ParkedBuffers
     lib = _lib.load()
+    monkeypatch.setattr(VecPogema, "PLAIN_CANDIDATES", 0)
     cfg = GridConfig(size=32, num_agents=32, obs_radius=5, density=0.3, seed=3, collision_system="soft")
     B = 3000  # 139 MB per observation tensor -> two output sets from the pool
     acts = torch.randint(0, 5, (4, B, 32), device="cuda", dtype=torch.int8)
@@ -367,11 +370,9 @@ def test_closed_environments_leave_their_buffers_to_the_next_one(monkeypatch):
     assert torch.equal(a.step(acts[0])[0], want[0])
     a.close()
     pygc.collect()
-    if len(a._zone_ptrs) == 2:  # (the candidate timing may prefer one of torch's own buffers: then no whole zone set exists)
-        assert len(ParkedBuffers._shelf[key]) == 1 and len(ParkedBuffers._shelf[key][0][0]) == 2
-        assert ParkedBuffers.bytes_parked() == 2 * B * 32 * 3 * 121 * 4
-    else:
-        pytest.skip("the pool's buffers lost the candidate timing on this box: nothing to park")
+    assert len(a._zone_ptrs) == 2, a.placement
+    assert len(ParkedBuffers._shelf[key]) == 1 and len(ParkedBuffers._shelf[key][0][0]) == 2
+    assert ParkedBuffers.bytes_parked() == 2 * B * 32 * 3 * 121 * 4
 
     va = int(lib.pgx_buffers_va_reserved())
     b = VecPogema(cfg, batch=B, auto_reset=True, placement_budget_gib="half")
@@ -397,9 +398,9 @@ def test_closed_environments_leave_their_buffers_to_the_next_one(monkeypatch):
     WalkVerdicts.clear()
     d = VecPogema(cfg, batch=B, auto_reset=True, placement_budget_gib="half")
     d.reset(seed=3)
-    whole = len(d._zone_ptrs) == 2
+    assert len(d._zone_ptrs) == 2, d.placement
     d.close()
-    assert (ParkedBuffers.bytes_parked() > 0) == whole
+    assert ParkedBuffers.bytes_parked() > 0
     e = VecPogema(cfg, batch=4, auto_reset=True)
     e.close(release=True)  # ... gives back what earlier environments left behind, too
     assert ParkedBuffers.bytes_parked() == 0
