@@ -309,6 +309,25 @@ int pgx_rollout(pgx_env* env, int32_t steps, const pgx_rollout_io* io, void* str
  * are not touched.  Asynchronous on `stream`. */
 int pgx_set_targets(pgx_env* env, const int32_t* target_xy, const uint8_t* agent_mask, void* stream);
 
+/* Shortest-path expert (docs/SPEC.md "Shortest-path expert"), read from the current device state -- the state the next
+ * pgx_step reads, which this call does not change.  For every agent:
+ *   distance  device i32 [batch, agents]   length of a shortest 4-connected path from the agent's cell to its current
+ *             target over the free cells of the height x width map (cells outside it are never traversed, whatever
+ *             random_outside says); 0 on the target; -1 when there is no path or the agent is not active (bit 0 of
+ *             is_active clear).  May be NULL.
+ *   actions   device [batch, agents] of action_dtype (PGX_ACTION_*): the lowest of 1..4 (up, down, left, right) whose
+ *             neighbour cell is at distance d - 1; 0 when d <= 0.
+ *   flags     PGX_EXPERT_AGENTS_AS_OBSTACLES: the cell of every OTHER active agent is blocked too (never the agent's own
+ *             cell or its own target cell).
+ * Replaces a host BFS per agent over `Grid.get_obstacles` (upstream's A* baseline pogema/a_star_policy.py plans on its
+ * remembered observations instead).  Asynchronous on `stream`, no host sync, capturable in a HIP graph.
+ * PGX_E_STATE before the first reset, like pgx_step.
+ * Maps wider or taller than 64: the first call with PGX_EXPERT_AGENTS_AS_OBSTACLES allocates 4 * batch * height *
+ * ceil(width / 32) bytes of device scratch (an occupancy bitmap) that the handle keeps; made inside a graph capture, that
+ * first call returns PGX_E_STATE instead -- make it once outside the capture. */
+#define PGX_EXPERT_AGENTS_AS_OBSTACLES 1
+int pgx_expert_actions(pgx_env* env, int32_t flags, void* actions, int32_t action_dtype, int32_t* distance, void* stream);
+
 /* Number of out-of-range actions (outside 0..4) that ACTIVE agents submitted since the last call (bad_action =
  * PGX_BAD_ACTION_FLAG only; otherwise always 0).  Inactive agents' actions are never looked at, as in the reference's
  * `if self.grid.is_active[agent_idx]` guards.  Synchronises `stream`, then clears the counter.  The host side turns a

@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "pgx_snapshot_bytes", "pgx_save_snapshot", "pgx_load_snapshot", "pgx_time_observe", "pgx_bad_action_count",
     "pgx_buffers_create", "pgx_buffers_ptr", "pgx_buffers_get_info", "pgx_buffers_destroy", "pgx_set_targets",
     "pgx_np_streams", "pgx_np_streams_host", "pgx_np_generate", "pgx_np_generate_host", "pgx_rollout", "pgx_buffers_stride", "pgx_buffers_drop", "pgx_xcd_shares", "pgx_xcd_tune", "pgx_buffers_create_at", "pgx_time_observe_pair", "pgx_buffers_va_reserved", "pgx_get_geometry",
+    "pgx_expert_actions",
 )
 
 
@@ -169,6 +170,8 @@ def load() -> C.CDLL:
     lib.pgx_buffers_stride.restype = C.c_int64
     lib.pgx_rollout.argtypes = [vp, i32, C.POINTER(PgxRolloutIO), vp]
     lib.pgx_rollout.restype = C.c_int
+    lib.pgx_expert_actions.argtypes = [vp, i32, vp, i32, vp, vp]
+    lib.pgx_expert_actions.restype = C.c_int
     lib.pgx_set_targets.argtypes = [vp, vp, vp, vp]
     lib.pgx_set_targets.restype = C.c_int
     lib.pgx_bad_action_count.argtypes = [vp, vp]

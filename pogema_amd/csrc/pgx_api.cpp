@@ -109,6 +109,8 @@ struct pgx_env {
     uint32_t* regen_fail = nullptr;       // [1] sticky failure counter of pgx_regenerate
     uint32_t* bad_count = nullptr;        // [1] out-of-range actions (bad_action = FLAG)
     float xcd_w[8] = {0.125f, 0.125f, 0.125f, 0.125f, 0.125f, 0.125f, 0.125f, 0.125f};  // shares of a launch per XCD
+    uint32_t* expert_occ = nullptr;       // [B][H][ceil(W/32)] occupancy bits of pgx_expert_actions' large-map layout
+                                          // (allocated by its first call with agents as obstacles)
     uint32_t *labels = nullptr, *pending = nullptr;  // [chunk_envs][H*W], allocated on first use
     uint8_t* scratch_map = nullptr;       // [chunk_envs][H*W] draft maps
     int chunk_envs = 0;
@@ -312,6 +314,12 @@ int pgx_create(const pgx_config* cfg, int device, pgx_env** out) {
         pgx_destroy(e);
         return fail(PGX_E_HIP, "cannot configure the step kernel (%zu bytes of LDS): %s", need, msg);
     }
+    err = pgx::prepare_expert(cfg->height, cfg->width);
+    if (err != hipSuccess) {
+        const char* msg = hipGetErrorString(err);
+        pgx_destroy(e);
+        return fail(PGX_E_HIP, "cannot configure the expert kernel: %s", msg);
+    }
     if (e->flags & 4u) {  // diagnostic time stamps, one record per workgroup
         e->dbg_elems = (size_t)cfg->batch * 4;
         if (hipMalloc((void**)&e->dbg, e->dbg_elems * sizeof(unsigned long long)) != hipSuccess) e->dbg = nullptr;
@@ -327,7 +335,7 @@ int pgx_destroy(pgx_env* e) {
     void* ptrs[] = {e->obst,   e->pos,     e->tgt,        e->pos0,     e->tgt0,       e->active,
                     e->elapsed, e->comp_begin, e->comp_len, e->comp_cells, e->tcount, e->np_state, e->np_state0, e->dbg, e->macc,
                     e->map_u8, e->todo, e->regen, e->epoch, e->fail_count, e->regen_fail, e->bad_count, e->labels, e->pending,
-                    e->scratch_map};
+                    e->scratch_map, e->expert_occ};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete e;
@@ -763,6 +771,53 @@ int pgx_rollout(pgx_env* e, int32_t steps, const pgx_rollout_io* io, void* strea
         p.xcd_base[x] = e->geo_roll.xcd_base[x];
     }
     PGX_HIP(pgx::launch_rollout(p, rp, e->geo_roll, (hipStream_t)stream));
+    return PGX_OK;
+}
+
+int pgx_expert_actions(pgx_env* e, int32_t flags, void* actions, int32_t action_dtype, int32_t* distance, void* stream) {
+    if (!e || !actions) return fail(PGX_E_INVALID, "pgx_expert_actions: null argument");
+    if (action_dtype < 0 || action_dtype > 2)
+        return fail(PGX_E_INVALID, "pgx_expert_actions: bad action_dtype %d", action_dtype);
+    if (flags & ~PGX_EXPERT_AGENTS_AS_OBSTACLES) return fail(PGX_E_INVALID, "pgx_expert_actions: unknown flags 0x%x", flags);
+    if (!e->has_state) return fail(PGX_E_STATE, "pgx_expert_actions called before pgx_reset_from_state");
+    DeviceGuard guard(e->device);
+    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
+    const bool with_agents = (flags & PGX_EXPERT_AGENTS_AS_OBSTACLES) != 0;
+    const size_t occ_words = pgx::expert_occupancy_words(e->cfg.batch, e->cfg.height, e->cfg.width);
+    if (with_agents && occ_words && !e->expert_occ) {
+        // the large-map layout's occupancy scratch: allocated on first use, so that step-only callers never pay for it
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        PGX_HIP(hipStreamIsCapturing((hipStream_t)stream, &cap));
+        if (cap != hipStreamCaptureStatusNone)
+            return fail(PGX_E_STATE, "pgx_expert_actions: the first call with PGX_EXPERT_AGENTS_AS_OBSTACLES on maps wider or "
+                                     "taller than 64 allocates %zu bytes of scratch; make it once outside graph capture",
+                        occ_words * sizeof(uint32_t));
+        const hipError_t err = hipMalloc((void**)&e->expert_occ, occ_words * sizeof(uint32_t));
+        if (err != hipSuccess) {
+            e->expert_occ = nullptr;
+            return fail(err == hipErrorOutOfMemory ? PGX_E_NOMEM : PGX_E_HIP,
+                        "pgx_expert_actions: occupancy scratch of %zu bytes: %s", occ_words * sizeof(uint32_t),
+                        hipGetErrorString(err));
+        }
+    }
+    pgx::ExpertParams p{};
+    p.batch = e->cfg.batch;
+    p.A = e->cfg.num_agents;
+    p.H = e->cfg.height;
+    p.W = e->cfg.width;
+    p.r = e->cfg.obs_radius;
+    p.wpr = e->wpr;
+    p.bmw = e->bmw;
+    p.with_agents = with_agents ? 1 : 0;
+    p.action_dtype = action_dtype;
+    p.obst = e->obst;
+    p.pos = e->pos;
+    p.tgt = e->tgt;
+    p.active = e->active;
+    p.occ = e->expert_occ;
+    p.actions = actions;
+    p.distance = distance;
+    PGX_HIP(pgx::launch_expert(p, (hipStream_t)stream));
     return PGX_OK;
 }
 

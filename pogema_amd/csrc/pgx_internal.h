@@ -149,6 +149,9 @@ struct StepGeometry {
 StepGeometry step_geometry(int batch, int A, int bmw, int W, bool allow_p16, int epw_override, int obs_elem_bytes,
                            int waves_override, bool for_rollout = false);
 hipError_t prepare_step(const StepGeometry& g, const StepGeometry& roll);
+// the > 48 KB dynamic-LDS opt-in of kernel `fn` on the current device: only ever raised, never lowered (an attribute of
+// the function, shared by every live handle; pgx_kernels.hip)
+hipError_t raise_lds_limit(const void* fn, size_t lds_bytes);
 hipError_t launch_step(const StepParams& p, const StepGeometry& g, hipStream_t stream);
 // splits `blocks` workgroups over the XCDs by `w`; returns the grid size (8 * the largest share)
 int xcd_partition(int blocks, const float w[8], int32_t n[8], int32_t base[8]);
@@ -204,5 +207,22 @@ hipError_t launch_unpack_state(const uint32_t* pos, const uint32_t* tgt, const u
                                int32_t* target_xy, uint8_t* act_out, size_t n, int r, hipStream_t stream);
 hipError_t launch_occupancy(const uint32_t* pos, const uint8_t* active, uint8_t* occ, size_t n, int A, int PH,
                             int PW, hipStream_t stream);
+
+// ---- shortest-path expert (pgx_expert.hip) ------------------------------------------------------------
+struct ExpertParams {
+    int32_t batch, A, H, W, r, wpr, bmw;
+    int32_t with_agents;     // other active agents block their cells
+    int32_t action_dtype;    // PGX_ACTION_*
+    const uint32_t* obst;    // [B][bmw] padded obstacle bitmaps
+    const uint32_t *pos, *tgt;
+    const uint8_t* active;
+    uint32_t* occ;           // [B][H][ceil(W/32)] occupancy scratch of the large layout (expert_occupancy_words)
+    void* actions;           // [B][A] of action_dtype
+    int32_t* distance;       // [B][A], may be null
+};
+bool expert_large_layout(int H, int W);
+size_t expert_occupancy_words(int batch, int H, int W);
+hipError_t prepare_expert(int H, int W);
+hipError_t launch_expert(const ExpertParams& p, hipStream_t stream);
 
 }  // namespace pgx

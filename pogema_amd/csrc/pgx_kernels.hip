@@ -1604,7 +1604,6 @@ StepGeometry step_geometry(int batch, int A, int bmw, int W, bool allow_p16, int
 // once per handle (NOT per launch: keeps pgx_step capturable in a HIP graph).  The > 48 KB opt-in is an attribute of
 // the kernel FUNCTION on a device, not of a handle: two live handles may share a template instance with different LDS
 // needs, so the limit is only ever raised (largest request so far per function and device).
-static hipError_t raise_lds_limit(const void* fn, size_t lds_bytes);
 static const void* rollout_fn_for(const StepGeometry& g);
 
 hipError_t prepare_step(const StepGeometry& g, const StepGeometry& roll) {
@@ -1615,7 +1614,7 @@ hipError_t prepare_step(const StepGeometry& g, const StepGeometry& roll) {
     return raise_lds_limit(rfn, roll.lds_bytes);
 }
 
-static hipError_t raise_lds_limit(const void* fn, size_t lds_bytes) {
+hipError_t raise_lds_limit(const void* fn, size_t lds_bytes) {
     if (lds_bytes <= 48 * 1024) return hipSuccess;
     static std::mutex mu;
     static std::map<std::pair<const void*, int>, size_t> granted;

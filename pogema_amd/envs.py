@@ -174,6 +174,11 @@ class Pogema:
         return ([obs[i] for i in range(obs.shape[0])], [float(x) for x in v["rewards"]],
                 [bool(x) for x in v["terminated"]], [bool(x) for x in v["truncated"]], info_list)
 
+    def expert_actions(self, agents_as_obstacles: bool = False):
+        """The shortest-path expert's action for every agent (VecPogema.expert_actions), as a list for step()."""
+        actions, _ = self._vec.expert_actions(agents_as_obstacles=agents_as_obstacles)
+        return [int(a) for a in actions[0].cpu().numpy()]
+
     def _metrics_dict(self, values):
         from ._lib import METRIC_NAMES
         metrics = {k: float(x) for k, x in zip(METRIC_NAMES, values)}

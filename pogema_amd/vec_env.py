@@ -694,6 +694,35 @@ class VecPogema(PlacementMixin):
         _lib.check(self._lib.pgx_set_targets(self._handle, t.data_ptr(), m.data_ptr() if m is not None else None,
                                              self._stream()))
 
+    def expert_actions(self, agents_as_obstacles: bool = False, dtype=torch.int64, out=None):
+        """Shortest-path expert (docs/SPEC.md "Shortest-path expert"), computed on the device from the current state --
+        the state the next step() reads, which this call leaves untouched.  Returns (actions [batch, agents] of `dtype`,
+        distance int32 [batch, agents]): distance is the 4-connected BFS distance from each agent to its target over the
+        map's free cells (0 on the target, -1 without a path or for an inactive agent); the action is the lowest of
+        1..4 (up, down, left, right) that lowers it, 0 when the distance is <= 0.  `agents_as_obstacles=True`: the
+        cells of the other active agents are blocked too.  Stream-ordered, no host sync, capturable in a HIP graph.
+        `out=(actions, distance)`: caller-owned contiguous tensors on this device (actions int8 / int32 / int64)."""
+        B, A = self.batch, self.num_agents
+        if out is not None:
+            if len(out) != 2:
+                raise ValueError("out must be (actions, distance)")
+            actions, distance = out
+            if (actions.dtype not in self._ACTION_CODE or tuple(actions.shape) != (B, A) or not actions.is_contiguous()
+                    or actions.device != self.device):
+                raise ValueError(f"out[actions] must be a contiguous int8 / int32 / int64 tensor of shape {(B, A)} on "
+                                 f"{self.device}")
+            if (distance.dtype != torch.int32 or tuple(distance.shape) != (B, A) or not distance.is_contiguous()
+                    or distance.device != self.device):
+                raise ValueError(f"out[distance] must be a contiguous int32 tensor of shape {(B, A)} on {self.device}")
+        else:
+            if dtype not in self._ACTION_CODE:
+                raise ValueError(f"dtype must be one of torch.int8, torch.int32, torch.int64, got {dtype}")
+            actions = torch.empty((B, A), dtype=dtype, device=self.device)
+            distance = torch.empty((B, A), dtype=torch.int32, device=self.device)
+        _lib.check(self._lib.pgx_expert_actions(self._handle, 1 if agents_as_obstacles else 0, actions.data_ptr(),
+                                                self._ACTION_CODE[actions.dtype], distance.data_ptr(), self._stream()))
+        return actions, distance
+
     def _wrap_obs(self, obs: torch.Tensor):
         """'default': the float32 tensor.  'POMAPF' / 'MAPF' (upstream `PogemaBase._pomapf_obs` / `_mapf_obs`):
         dict views over the same planes plus coordinates relative to each agent's start cell (and, for MAPF,
