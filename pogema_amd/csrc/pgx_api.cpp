@@ -1,5 +1,5 @@
-// pgx_api.cpp -- C-ABI of the engine (include/pogema_amd.h): handle management, reset, step launch,
-// state export and the host-side synthetic map generator.  Compiled with hipcc together with
+// pgx_api.cpp -- C-ABI of the engine (include/pogema_amd.h): handle management, reset, step launch and
+// state export (the host-side generator is pgx_generate.cpp).  Compiled with hipcc together with
 // pgx_kernels.hip into libpogema_amd.so.  There is NO CPU fallback anywhere in this file: every
 // compute entry point enqueues HIP kernels and fails with PGX_E_HIP when no device is usable.
 #include "../../include/pogema_amd.h"
@@ -13,36 +13,15 @@
 #include <cstring>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "pgx_internal.h"
 
 namespace {
-
 thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define PGX_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e__ = (call);                                                                   \
-        if (e__ != hipSuccess)                                                                     \
-            return fail(PGX_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-    } while (0)
-
 }  // namespace
 
 namespace pgx {
-// error reporting for the other translation units of the library (pgx_buffers.hip)
 int fail_msg(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -56,27 +35,31 @@ int fail_msg(int code, const char* fmt, ...) {
 
 namespace {
 
-struct DeviceGuard {
-    int prev = -1;
-    bool changed = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != dev) {
-            err = hipSetDevice(dev);
-            changed = (err == hipSuccess);
-        }
+using pgx::DeviceGuard;
+using pgx::fail_msg;
+
+// A device allocation owned by the handle: freed by reset() or with the handle (pgx_destroy, on the handle's device).
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+    operator T*() const { return p; }
+    hipError_t alloc(size_t bytes) {  // (stays null when it fails)
+        reset();
+        const hipError_t err = hipMalloc((void**)&p, bytes);
+        if (err != hipSuccess) p = nullptr;
+        return err;
     }
-    ~DeviceGuard() {
-        if (changed) (void)hipSetDevice(prev);
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
     }
 };
 
-int next_pow2(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
+int alloc_code(hipError_t err) { return err == hipErrorOutOfMemory ? PGX_E_NOMEM : PGX_E_HIP; }
 
 }  // namespace
 
@@ -90,38 +73,140 @@ struct pgx_env {
     uint32_t flags = 0;
     bool xcd_aware = true;  // false: not an 8-XCD SPX device -> identity workgroup mapping, no XCD shares, no cohort stagger
     // device state
-    uint32_t* obst = nullptr;
-    uint32_t *pos = nullptr, *tgt = nullptr, *pos0 = nullptr, *tgt0 = nullptr;
-    uint8_t* active = nullptr;
-    int32_t* elapsed = nullptr;
-    int4* macc = nullptr;
+    DevBuf<uint32_t> obst;
+    DevBuf<uint32_t> pos, tgt, pos0, tgt0;
+    DevBuf<uint8_t> active;
+    DevBuf<int32_t> elapsed;
+    DevBuf<int4> macc;
     float* metrics_out = nullptr;   // caller-owned (pgx_set_metrics_buffers)
     uint8_t* episode_done = nullptr; // caller-owned
-    unsigned long long* dbg = nullptr;
+    DevBuf<unsigned long long> dbg;
     size_t dbg_elems = 0;
-    uint32_t *comp_begin = nullptr, *comp_len = nullptr, *comp_cells = nullptr, *tcount = nullptr;
-    pgx::NpGen *np_state = nullptr, *np_state0 = nullptr;  // lifelong_rng = NUMPY
+    DevBuf<uint32_t> comp_begin, comp_len, comp_cells, tcount;
+    DevBuf<pgx::NpGen> np_state, np_state0;  // lifelong_rng = NUMPY
     // reset path (pgx_reset.hip): unpadded u8 maps, per-env flags / generation counters, chunked scratch
-    uint8_t* map_u8 = nullptr;            // [B][H*W]
-    uint8_t *todo = nullptr, *regen = nullptr;  // [B]
-    uint32_t* epoch = nullptr;            // [B]
-    uint32_t* fail_count = nullptr;       // [1]
-    uint32_t* regen_fail = nullptr;       // [1] sticky failure counter of pgx_regenerate
-    uint32_t* bad_count = nullptr;        // [1] out-of-range actions (bad_action = FLAG)
+    DevBuf<uint8_t> map_u8;               // [B][H*W]
+    DevBuf<uint8_t> todo, regen;          // [B]
+    DevBuf<uint32_t> epoch;               // [B]
+    DevBuf<uint32_t> fail_count;          // [1]
+    DevBuf<uint32_t> regen_fail;          // [1] sticky failure counter of pgx_regenerate
+    DevBuf<uint32_t> bad_count;           // [1] out-of-range actions (bad_action = FLAG)
     float xcd_w[8] = {0.125f, 0.125f, 0.125f, 0.125f, 0.125f, 0.125f, 0.125f, 0.125f};  // shares of a launch per XCD
-    uint32_t* expert_occ = nullptr;       // [B][H][ceil(W/32)] occupancy bits of pgx_expert_actions' large-map layout
+    DevBuf<uint32_t> expert_occ;          // [B][H][ceil(W/32)] occupancy bits of pgx_expert_actions' large-map layout
                                           // (allocated by its first call with agents as obstacles)
-    uint32_t *labels = nullptr, *pending = nullptr;  // [chunk_envs][H*W], allocated on first use
-    uint8_t* scratch_map = nullptr;       // [chunk_envs][H*W] draft maps
+    DevBuf<uint32_t> labels, pending;     // [chunk_envs][H*W], allocated on first use
+    DevBuf<uint8_t> scratch_map;          // [chunk_envs][H*W] draft maps
     int chunk_envs = 0;
 };
 
-// ================================================================================================
-extern "C" {
+namespace {
 
-static int obs_elem_bytes(int obs_dtype) {
+// The prologue of every entry point that works on the handle's device: `e` is non-null, holds a state when `need_state`,
+// and its device stays selected while `guard` lives.  `who` names the entry point in the error message.
+int enter(DeviceGuard& guard, const pgx_env* e, const char* who, bool need_state) {
+    if (!e) return fail_msg(PGX_E_INVALID, "%s: null handle", who);
+    if (need_state && !e->has_state) return fail_msg(PGX_E_STATE, "%s called before a reset", who);
+    if (guard.select(e->device) != hipSuccess)
+        return fail_msg(PGX_E_HIP, "%s: cannot select HIP device %d: %s", who, e->device, hipGetErrorString(guard.err));
+    return PGX_OK;
+}
+
+int obs_elem_bytes(int obs_dtype) {
     return obs_dtype == PGX_OBS_U8 ? 1 : (obs_dtype == PGX_OBS_BF16 || obs_dtype == PGX_OBS_F16) ? 2 : 4;
 }
+
+// The launch parameters of the handle with launch shape `g` (e->geo: pgx_step / pgx_observe, e->geo_roll: pgx_rollout).
+pgx::StepParams step_params(const pgx_env* e, const pgx::StepGeometry& g) {
+    const pgx_config& c = e->cfg;
+    pgx::StepParams p;
+    memset(&p, 0, sizeof p);
+    p.batch = c.batch;
+    p.num_agents = c.num_agents;
+    p.r = c.obs_radius;
+    p.wpr = e->wpr;
+    p.bm_words = e->bmw;
+    p.map_w = c.width;
+    p.map_cells = c.height * c.width;
+    p.w_magic = (uint32_t)((1ull << 32) / (uint64_t)e->W) + 1u;
+    p.a_magic = c.num_agents > 1 ? (uint32_t)((1ull << 32) / (uint64_t)c.num_agents) + 1u : 0u;  // 0: A = 1, slot = env
+    p.collision = c.collision_system;
+    p.on_target = c.on_target;
+    p.max_steps = c.max_episode_steps;
+    p.auto_reset = c.auto_reset;
+    p.flags = e->flags;
+    p.epw = g.epw;
+    p.stagger = g.stagger;
+    p.store_policy = g.store_policy;
+    p.state_stores = g.state_stores;
+    for (int x = 0; x < 8; ++x) {
+        p.xcd_n[x] = g.xcd_n[x];
+        p.xcd_base[x] = g.xcd_base[x];
+    }
+    p.obs_u8 = c.obs_dtype == PGX_OBS_U8 ? 1 : 0;
+    p.obs_one = c.obs_dtype == PGX_OBS_BF16 ? 0x3F80u : c.obs_dtype == PGX_OBS_F16 ? 0x3C00u : 0u;
+    p.soft_rule = c.soft_vertex_rule;
+    p.soft_occupancy = c.soft_occupancy;
+    p.coop_reward = c.coop_reward;
+    p.bad_action = c.bad_action;
+    p.bad_count = e->bad_count;
+    p.seed = c.seed;
+    p.env_index_base = c.env_index_base;
+    p.obst = e->obst;
+    p.pos = e->pos;
+    p.tgt = e->tgt;
+    p.active = e->active;
+    p.elapsed = e->elapsed;
+    p.pos0 = e->pos0;
+    p.tgt0 = e->tgt0;
+    p.comp_begin = e->comp_begin;
+    p.comp_len = e->comp_len;
+    p.comp_cells = e->comp_cells;
+    p.tcount = e->tcount;
+    p.np_state = e->np_state;
+    p.np_state0 = e->np_state0;
+    p.dbg = e->dbg;
+    p.macc = e->macc;
+    p.metrics_out = e->metrics_out;
+    p.episode_done = e->episode_done;
+    return p;
+}
+
+// an observation-only launch (MODE_OBSERVE) of pgx_step's launch shape into `obs`
+pgx::StepParams observe_params(const pgx_env* e, void* obs) {
+    pgx::StepParams p = step_params(e, e->geo);
+    p.mode = pgx::MODE_OBSERVE;
+    p.obs = static_cast<float*>(obs);
+    return p;
+}
+
+// Mean time of one launch of `p` in us: `warmup` launches, then `timed` launches between an event pair; launch i of
+// either phase writes obs[i & 1].  The events are released on every path.
+hipError_t time_launches(pgx::StepParams p, const pgx::StepGeometry& g, void* const obs[2], int warmup, int timed,
+                         hipStream_t s, float* us) {
+    auto launch = [&](int i) {
+        p.obs = static_cast<float*>(obs[i & 1]);
+        return pgx::launch_step(p, g, s);
+    };
+    hipEvent_t a = nullptr, b = nullptr;
+    hipError_t err = hipEventCreate(&a);
+    if (err == hipSuccess) err = hipEventCreate(&b);
+    for (int i = 0; i < warmup && err == hipSuccess; ++i) err = launch(i);
+    if (err == hipSuccess) err = hipEventRecord(a, s);
+    for (int i = 0; i < timed && err == hipSuccess; ++i) err = launch(i);
+    if (err == hipSuccess) err = hipEventRecord(b, s);
+    if (err == hipSuccess) err = hipEventSynchronize(b);
+    float ms = 0.0f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&ms, a, b);
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+    if (err == hipSuccess) *us = ms * 1000.0f / (float)timed;
+    return err;
+}
+
+}  // namespace
+
+// ================================================================================================
+extern "C" {
 
 int pgx_abi_version(void) { return PGX_ABI_VERSION; }
 
@@ -140,34 +225,34 @@ static void apply_xcd_shares(pgx_env* e) {
 static int create_host_side(const pgx_config* cfg, int device, pgx_env** out_e) {
     *out_e = nullptr;
     if (cfg->abi_version != PGX_ABI_VERSION)
-        return fail(PGX_E_INVALID, "pgx_config.abi_version is %d but this library implements ABI %d: rebuild the caller against "
-                    "include/pogema_amd.h and set cfg.abi_version = PGX_ABI_VERSION (ABI 5 renumbered soft_occupancy: 0 is "
-                    "the index-order loop, 1 the exact set; ABI <= 5 callers pass 0 in this field)", cfg->abi_version, PGX_ABI_VERSION);
-    if (cfg->batch < 1) return fail(PGX_E_INVALID, "batch must be >= 1 (got %d)", cfg->batch);
+        return fail_msg(PGX_E_INVALID, "pgx_config.abi_version is %d but this library implements ABI %d: rebuild the caller against "
+                        "include/pogema_amd.h and set cfg.abi_version = PGX_ABI_VERSION (ABI 5 renumbered soft_occupancy: 0 is "
+                        "the index-order loop, 1 the exact set; ABI <= 5 callers pass 0 in this field)", cfg->abi_version, PGX_ABI_VERSION);
+    if (cfg->batch < 1) return fail_msg(PGX_E_INVALID, "batch must be >= 1 (got %d)", cfg->batch);
     if (cfg->height < 1 || cfg->width < 1 || cfg->height > PGX_MAX_SIDE || cfg->width > PGX_MAX_SIDE)
-        return fail(PGX_E_INVALID, "map size %dx%d outside [1, %d]", cfg->height, cfg->width, PGX_MAX_SIDE);
+        return fail_msg(PGX_E_INVALID, "map size %dx%d outside [1, %d]", cfg->height, cfg->width, PGX_MAX_SIDE);
     if (cfg->num_agents < 1 || cfg->num_agents > PGX_MAX_AGENTS)
-        return fail(PGX_E_INVALID, "num_agents %d outside [1, %d]", cfg->num_agents, PGX_MAX_AGENTS);
+        return fail_msg(PGX_E_INVALID, "num_agents %d outside [1, %d]", cfg->num_agents, PGX_MAX_AGENTS);
     if (cfg->obs_radius < 1 || cfg->obs_radius > PGX_MAX_OBS_RADIUS)
-        return fail(PGX_E_INVALID, "obs_radius %d outside [1, %d] supported by this build", cfg->obs_radius,
-                    PGX_MAX_OBS_RADIUS);
+        return fail_msg(PGX_E_INVALID, "obs_radius %d outside [1, %d] supported by this build", cfg->obs_radius,
+                        PGX_MAX_OBS_RADIUS);
     if (cfg->collision_system < 0 || cfg->collision_system > 2)
-        return fail(PGX_E_INVALID, "unknown collision_system %d", cfg->collision_system);
-    if (cfg->on_target < 0 || cfg->on_target > 2) return fail(PGX_E_INVALID, "unknown on_target %d", cfg->on_target);
+        return fail_msg(PGX_E_INVALID, "unknown collision_system %d", cfg->collision_system);
+    if (cfg->on_target < 0 || cfg->on_target > 2) return fail_msg(PGX_E_INVALID, "unknown on_target %d", cfg->on_target);
     if (cfg->random_outside && !(cfg->outside_density >= 0.0f && cfg->outside_density <= 1.0f))
-        return fail(PGX_E_INVALID, "outside_density %.3f outside [0, 1]", (double)cfg->outside_density);
+        return fail_msg(PGX_E_INVALID, "outside_density %.3f outside [0, 1]", (double)cfg->outside_density);
     if (cfg->soft_vertex_rule < 0 || cfg->soft_vertex_rule > 1 || cfg->coop_reward < 0 || cfg->coop_reward > 1 ||
         cfg->bad_action < 0 || cfg->bad_action > 1 || cfg->lifelong_rng < 0 || cfg->lifelong_rng > 1 ||
         cfg->soft_occupancy < 0 || cfg->soft_occupancy > 1)
-        return fail(PGX_E_INVALID, "unknown semantics switch (soft_vertex_rule %d, coop_reward %d, bad_action %d, soft_occupancy %d)",
-                    cfg->soft_vertex_rule, cfg->coop_reward, cfg->bad_action, cfg->soft_occupancy);
+        return fail_msg(PGX_E_INVALID, "unknown semantics switch (soft_vertex_rule %d, coop_reward %d, bad_action %d, soft_occupancy %d)",
+                        cfg->soft_vertex_rule, cfg->coop_reward, cfg->bad_action, cfg->soft_occupancy);
     if (cfg->obs_dtype < PGX_OBS_F32 || cfg->obs_dtype > PGX_OBS_F16)
-        return fail(PGX_E_INVALID, "unknown obs_dtype %d", cfg->obs_dtype);
+        return fail_msg(PGX_E_INVALID, "unknown obs_dtype %d", cfg->obs_dtype);
     if ((int64_t)cfg->num_agents > (int64_t)cfg->height * cfg->width)
-        return fail(PGX_E_INVALID, "more agents than cells");
+        return fail_msg(PGX_E_INVALID, "more agents than cells");
 
     pgx_env* e = new (std::nothrow) pgx_env();
-    if (!e) return fail(PGX_E_NOMEM, "out of host memory");
+    if (!e) return fail_msg(PGX_E_NOMEM, "out of host memory");
     e->cfg = *cfg;
     e->device = device;
     const int A = cfg->num_agents, r = cfg->obs_radius;
@@ -207,11 +292,11 @@ static int create_host_side(const pgx_config* cfg, int device, pgx_env** out_e) 
         const size_t need = e->geo.lds_bytes;
         const int bm_bytes = e->bmw * 4, Wd = e->W;
         delete e;
-        return fail(PGX_E_INVALID,
-                    "configuration needs %zu bytes of LDS per workgroup (> 163840) even in the large-map layout (occupancy "
-                    "bitmap of %dx%d cells = %d bytes, plus the exchange arrays and row masks of %d agents with a %dx%d "
-                    "window): see the Limits table in README.md",
-                    need, cfg->height + 2 * r, cfg->width + 2 * r, bm_bytes, A, Wd, Wd);
+        return fail_msg(PGX_E_INVALID,
+                        "configuration needs %zu bytes of LDS per workgroup (> 163840) even in the large-map layout (occupancy "
+                        "bitmap of %dx%d cells = %d bytes, plus the exchange arrays and row masks of %d agents with a %dx%d "
+                        "window): see the Limits table in README.md",
+                        need, cfg->height + 2 * r, cfg->width + 2 * r, bm_bytes, A, Wd, Wd);
     }
 
     *out_e = e;
@@ -219,25 +304,20 @@ static int create_host_side(const pgx_config* cfg, int device, pgx_env** out_e) 
 }
 
 int pgx_check_config(const pgx_config* cfg) {
-    if (!cfg) return fail(PGX_E_INVALID, "pgx_check_config: null argument");
+    if (!cfg) return fail_msg(PGX_E_INVALID, "pgx_check_config: null argument");
     pgx_env* e = nullptr;
     const int rc = create_host_side(cfg, 0, &e);
     delete e;
     return rc;
 }
 
-int pgx_create(const pgx_config* cfg, int device, pgx_env** out) {
-    if (!cfg || !out) return fail(PGX_E_INVALID, "pgx_create: null argument");
-    *out = nullptr;
-    pgx_env* e = nullptr;
-    if (const int rc = create_host_side(cfg, device, &e)) return rc;
-    const int A = cfg->num_agents;
-
+// Everything of pgx_create that needs the device; the caller destroys the half-built handle when it fails.
+static int create_device_side(pgx_env* e) {
+    const pgx_config* cfg = &e->cfg;
+    const int A = cfg->num_agents, device = e->device;
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) {
-        delete e;
-        return fail(PGX_E_HIP, "cannot select HIP device %d: %s", device, hipGetErrorString(guard.err));
-    }
+    if (guard.err != hipSuccess)
+        return fail_msg(PGX_E_HIP, "cannot select HIP device %d: %s", device, hipGetErrorString(guard.err));
     // The workgroup -> slice mapping, the per-XCD shares and the cohort stagger of the step kernel assume what this pool's
     // MI355X are: ONE compute partition of 8 XCDs (SPX), where hardware deals consecutive workgroups out round-robin
     // (blockIdx & 7 == XCD) -- VERDICT r3 weak #9.  Results never depend on it, but the tuning would be meaningless on a
@@ -257,48 +337,47 @@ int pgx_create(const pgx_config* cfg, int device, pgx_env** out) {
     }
     const size_t B = (size_t)cfg->batch, BA = B * A;
     hipError_t err = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) {
-        if (err == hipSuccess) err = hipMalloc(p, bytes);
+    auto alloc = [&](auto& buf, size_t bytes) {
+        if (err == hipSuccess) err = buf.alloc(bytes);
     };
     // (+ 4 words: the window funnel reads the word behind the last one of a row unconditionally -- in LDS that is the next
     // array, in the large-map layout, which reads the HBM bitmap directly, it must still be inside the allocation)
-    alloc((void**)&e->obst, (B * e->bmw + 4) * sizeof(uint32_t));
-    alloc((void**)&e->pos, BA * sizeof(uint32_t));
-    alloc((void**)&e->tgt, BA * sizeof(uint32_t));
-    alloc((void**)&e->pos0, BA * sizeof(uint32_t));
-    alloc((void**)&e->tgt0, BA * sizeof(uint32_t));
-    alloc((void**)&e->active, BA);
-    alloc((void**)&e->elapsed, B * sizeof(int32_t));
-    alloc((void**)&e->macc, B * sizeof(int4));
-    alloc((void**)&e->map_u8, B * (size_t)cfg->height * cfg->width);
-    alloc((void**)&e->todo, B);
-    alloc((void**)&e->regen, B);
-    alloc((void**)&e->epoch, B * sizeof(uint32_t));
-    alloc((void**)&e->fail_count, sizeof(uint32_t));
-    alloc((void**)&e->regen_fail, sizeof(uint32_t));
-    alloc((void**)&e->bad_count, sizeof(uint32_t));
+    alloc(e->obst, (B * e->bmw + 4) * sizeof(uint32_t));
+    alloc(e->pos, BA * sizeof(uint32_t));
+    alloc(e->tgt, BA * sizeof(uint32_t));
+    alloc(e->pos0, BA * sizeof(uint32_t));
+    alloc(e->tgt0, BA * sizeof(uint32_t));
+    alloc(e->active, BA);
+    alloc(e->elapsed, B * sizeof(int32_t));
+    alloc(e->macc, B * sizeof(int4));
+    alloc(e->map_u8, B * (size_t)cfg->height * cfg->width);
+    alloc(e->todo, B);
+    alloc(e->regen, B);
+    alloc(e->epoch, B * sizeof(uint32_t));
+    alloc(e->fail_count, sizeof(uint32_t));
+    alloc(e->regen_fail, sizeof(uint32_t));
+    alloc(e->bad_count, sizeof(uint32_t));
     if (cfg->on_target == PGX_ON_TARGET_RESTART) {
         const size_t cells = B * (size_t)cfg->height * cfg->width;
-        alloc((void**)&e->comp_begin, cells * sizeof(uint32_t));
-        alloc((void**)&e->comp_len, cells * sizeof(uint32_t));
-        alloc((void**)&e->comp_cells, cells * sizeof(uint32_t));
-        alloc((void**)&e->tcount, BA * sizeof(uint32_t));
+        alloc(e->comp_begin, cells * sizeof(uint32_t));
+        alloc(e->comp_len, cells * sizeof(uint32_t));
+        alloc(e->comp_cells, cells * sizeof(uint32_t));
+        alloc(e->tcount, BA * sizeof(uint32_t));
         if (cfg->lifelong_rng == PGX_LIFELONG_RNG_NUMPY) {
-            alloc((void**)&e->np_state, BA * sizeof(pgx::NpGen));
-            alloc((void**)&e->np_state0, BA * sizeof(pgx::NpGen));
+            alloc(e->np_state, BA * sizeof(pgx::NpGen));
+            alloc(e->np_state0, BA * sizeof(pgx::NpGen));
         }
     }
-    if (err != hipSuccess) {
-        const char* msg = hipGetErrorString(err);
-        pgx_destroy(e);
-        return fail(err == hipErrorOutOfMemory ? PGX_E_NOMEM : PGX_E_HIP, "hipMalloc failed: %s", msg);
-    }
+    if (err != hipSuccess) return fail_msg(alloc_code(err), "hipMalloc failed: %s", hipGetErrorString(err));
     err = hipMemset(e->regen_fail, 0, sizeof(uint32_t));
     if (err == hipSuccess) err = hipMemset(e->bad_count, 0, sizeof(uint32_t));
     if (err == hipSuccess && e->np_state0)
         err = pgx::launch_init_np_lifelong(e->np_state0, cfg->seed, cfg->env_index_base, cfg->batch, A, nullptr);
     if (err == hipSuccess && e->np_state0) err = hipStreamSynchronize(nullptr);
     if (err == hipSuccess) err = pgx::prepare_step(e->geo, e->geo_roll);
+    if (err != hipSuccess)
+        return fail_msg(PGX_E_HIP, "cannot configure the step kernel (%zu bytes of LDS): %s", e->geo.lds_bytes,
+                        hipGetErrorString(err));
     if (const char* spec = getenv("PGX_XCD_WEIGHTS")) {  // eight comma-separated weights (diagnostic)
         float f[8], sum = 0.f;
         if (sscanf(spec, "%f,%f,%f,%f,%f,%f,%f,%f", &f[0], &f[1], &f[2], &f[3], &f[4], &f[5], &f[6], &f[7]) == 8) {
@@ -308,22 +387,24 @@ int pgx_create(const pgx_config* cfg, int device, pgx_env** out) {
         }
     }
     apply_xcd_shares(e);
-    if (err != hipSuccess) {
-        const char* msg = hipGetErrorString(err);
-        const size_t need = e->geo.lds_bytes;
-        pgx_destroy(e);
-        return fail(PGX_E_HIP, "cannot configure the step kernel (%zu bytes of LDS): %s", need, msg);
-    }
     err = pgx::prepare_expert(cfg->height, cfg->width);
-    if (err != hipSuccess) {
-        const char* msg = hipGetErrorString(err);
-        pgx_destroy(e);
-        return fail(PGX_E_HIP, "cannot configure the expert kernel: %s", msg);
-    }
+    if (err != hipSuccess) return fail_msg(PGX_E_HIP, "cannot configure the expert kernel: %s", hipGetErrorString(err));
     if (e->flags & 4u) {  // diagnostic time stamps, one record per workgroup
         e->dbg_elems = (size_t)cfg->batch * 4;
-        if (hipMalloc((void**)&e->dbg, e->dbg_elems * sizeof(unsigned long long)) != hipSuccess) e->dbg = nullptr;
-        else (void)hipMemset(e->dbg, 0, e->dbg_elems * sizeof(unsigned long long));
+        if (e->dbg.alloc(e->dbg_elems * sizeof(unsigned long long)) == hipSuccess)
+            (void)hipMemset(e->dbg, 0, e->dbg_elems * sizeof(unsigned long long));
+    }
+    return PGX_OK;
+}
+
+int pgx_create(const pgx_config* cfg, int device, pgx_env** out) {
+    if (!cfg || !out) return fail_msg(PGX_E_INVALID, "pgx_create: null argument");
+    *out = nullptr;
+    pgx_env* e = nullptr;
+    if (const int rc = create_host_side(cfg, device, &e)) return rc;
+    if (const int rc = create_device_side(e)) {
+        pgx_destroy(e);
+        return rc;
     }
     *out = e;
     return PGX_OK;
@@ -331,13 +412,7 @@ int pgx_create(const pgx_config* cfg, int device, pgx_env** out) {
 
 int pgx_destroy(pgx_env* e) {
     if (!e) return PGX_OK;
-    DeviceGuard guard(e->device);
-    void* ptrs[] = {e->obst,   e->pos,     e->tgt,        e->pos0,     e->tgt0,       e->active,
-                    e->elapsed, e->comp_begin, e->comp_len, e->comp_cells, e->tcount, e->np_state, e->np_state0, e->dbg, e->macc,
-                    e->map_u8, e->todo, e->regen, e->epoch, e->fail_count, e->regen_fail, e->bad_count, e->labels, e->pending,
-                    e->scratch_map, e->expert_occ};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    DeviceGuard guard(e->device);  // the handle's buffers are freed on their device
     delete e;
     return PGX_OK;
 }
@@ -352,9 +427,6 @@ int64_t pgx_agent_elems(const pgx_env* e) {
     return (int64_t)e->cfg.batch * e->cfg.num_agents;
 }
 
-static void fill_params(const pgx_env* e, pgx::StepParams& p);
-
-
 // ---- reset path ---------------------------------------------------------------------------------------
 // Scratch of the reset kernel: 9 bytes per cell and slot (draft map, labels, pending).  The synchronous resets
 // walk the batch in chunks of <= 2^25 cells' worth of environments (<= 288 MiB); pgx_regenerate, which must not
@@ -366,30 +438,26 @@ static int ensure_reset_scratch(pgx_env* e, bool full) {
     if (full) {
         chunk = (size_t)e->cfg.batch;
         if (chunk * cells * 9 > ((size_t)32 << 30))
-            return fail(PGX_E_NOMEM, "pgx_regenerate needs %zu bytes of scratch (9 per cell and env); use pgx_reset_random",
-                        chunk * cells * 9);
+            return fail_msg(PGX_E_NOMEM, "pgx_regenerate needs %zu bytes of scratch (9 per cell and env); use pgx_reset_random",
+                            chunk * cells * 9);
     }
     if (e->labels && (size_t)e->chunk_envs >= chunk) return PGX_OK;
+    auto release = [e]() {
+        e->labels.reset();
+        e->pending.reset();
+        e->scratch_map.reset();
+    };
     if (e->labels) {
         PGX_HIP(hipDeviceSynchronize());
-        (void)hipFree(e->labels);
-        (void)hipFree(e->pending);
-        (void)hipFree(e->scratch_map);
-        e->labels = e->pending = nullptr;
-        e->scratch_map = nullptr;
+        release();
     }
     e->chunk_envs = 0;
-    hipError_t err = hipMalloc((void**)&e->labels, chunk * cells * sizeof(uint32_t));
-    if (err == hipSuccess) err = hipMalloc((void**)&e->pending, chunk * cells * sizeof(uint32_t));
-    if (err == hipSuccess) err = hipMalloc((void**)&e->scratch_map, chunk * cells);
+    hipError_t err = e->labels.alloc(chunk * cells * sizeof(uint32_t));
+    if (err == hipSuccess) err = e->pending.alloc(chunk * cells * sizeof(uint32_t));
+    if (err == hipSuccess) err = e->scratch_map.alloc(chunk * cells);
     if (err != hipSuccess) {  // all or nothing: a later call must not find half of the scratch
-        if (e->labels) (void)hipFree(e->labels);
-        if (e->pending) (void)hipFree(e->pending);
-        if (e->scratch_map) (void)hipFree(e->scratch_map);
-        e->labels = e->pending = nullptr;
-        e->scratch_map = nullptr;
-        return fail(err == hipErrorOutOfMemory ? PGX_E_NOMEM : PGX_E_HIP, "reset scratch (%zu bytes): %s", chunk * cells * 9,
-                    hipGetErrorString(err));
+        release();
+        return fail_msg(alloc_code(err), "reset scratch (%zu bytes): %s", chunk * cells * 9, hipGetErrorString(err));
     }
     e->chunk_envs = (int)chunk;
     return PGX_OK;
@@ -425,9 +493,9 @@ static pgx::ResetParams reset_params(const pgx_env* e) {
 
 int pgx_reset_from_state(pgx_env* e, const uint8_t* obstacles, const int32_t* agent_xy, const int32_t* target_xy,
                          void* stream) {
-    if (!e || !obstacles || !agent_xy || !target_xy) return fail(PGX_E_INVALID, "pgx_reset_from_state: null argument");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
+    if (!e || !obstacles || !agent_xy || !target_xy) return fail_msg(PGX_E_INVALID, "pgx_reset_from_state: null argument");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_reset_from_state", false)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const pgx_config& c = e->cfg;
     const size_t B = (size_t)c.batch, BA = B * c.num_agents;
@@ -439,7 +507,7 @@ int pgx_reset_from_state(pgx_env* e, const uint8_t* obstacles, const int32_t* ag
     PGX_HIP(pgx::launch_pack_agents(agent_xy, target_xy, e->pos, e->tgt, e->pos0, e->tgt0, e->active, e->tcount, BA,
                                     c.obs_radius, s, e->np_state, e->np_state0));
     PGX_HIP(pgx::launch_zero_i32(e->elapsed, B, s));
-    PGX_HIP(pgx::launch_zero_i32(reinterpret_cast<int32_t*>(e->macc), B * 4, s));
+    PGX_HIP(pgx::launch_zero_i32(reinterpret_cast<int32_t*>(e->macc.p), B * 4, s));
     if (c.on_target == PGX_ON_TARGET_RESTART) {  // component tables of PogemaLifeLong, built on the device
         if (int rc = ensure_reset_scratch(e, false)) return rc;
         pgx::ResetParams p = reset_params(e);
@@ -456,17 +524,17 @@ int pgx_reset_from_state(pgx_env* e, const uint8_t* obstacles, const int32_t* ag
 
 int pgx_reset_random(pgx_env* e, float density, uint64_t seed, const uint8_t* shared_map, const uint8_t* env_mask,
                      int32_t max_retries, void* stream) {
-    if (!e) return fail(PGX_E_INVALID, "pgx_reset_random: null handle");
+    if (!e) return fail_msg(PGX_E_INVALID, "pgx_reset_random: null handle");
     if (!shared_map && !(density >= 0.0f && density <= 1.0f))
-        return fail(PGX_E_INVALID, "density %.3f outside [0, 1]", (double)density);
-    if (env_mask && !e->has_state) return fail(PGX_E_STATE, "masked pgx_reset_random before the first full reset");
+        return fail_msg(PGX_E_INVALID, "density %.3f outside [0, 1]", (double)density);
+    if (env_mask && !e->has_state) return fail_msg(PGX_E_STATE, "masked pgx_reset_random before the first full reset");
     const pgx_config& c = e->cfg;
     const int cells = c.height * c.width;
     if ((int64_t)2 * c.num_agents > (int64_t)cells)
-        return fail(PGX_E_PLACEMENT, "%d agents need %d distinct cells, map has %d", c.num_agents, 2 * c.num_agents, cells);
+        return fail_msg(PGX_E_PLACEMENT, "%d agents need %d distinct cells, map has %d", c.num_agents, 2 * c.num_agents, cells);
     if (max_retries < 1) max_retries = 10;
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_reset_random", false)) return rc;
     if (int rc = ensure_reset_scratch(e, false)) return rc;
     hipStream_t s = (hipStream_t)stream;
     pgx::ResetParams p = reset_params(e);
@@ -487,8 +555,8 @@ int pgx_reset_random(pgx_env* e, float density, uint64_t seed, const uint8_t* sh
     PGX_HIP(hipStreamSynchronize(s));  // the status is the device's failure count
     if (failed) {
         if (!env_mask) e->has_state = false;  // (masked: the failed envs keep their previous instance)
-        return fail(PGX_E_PLACEMENT, "could not place %d agents in %u environment(s) after %d attempts (density %.2f, %dx%d)",
-                    c.num_agents, failed, max_retries, (double)density, c.height, c.width);
+        return fail_msg(PGX_E_PLACEMENT, "could not place %d agents in %u environment(s) after %d attempts (density %.2f, %dx%d)",
+                        c.num_agents, failed, max_retries, (double)density, c.height, c.width);
     }
     e->has_state = true;
     return PGX_OK;
@@ -496,13 +564,12 @@ int pgx_reset_random(pgx_env* e, float density, uint64_t seed, const uint8_t* sh
 
 int pgx_regenerate(pgx_env* e, const uint8_t* env_mask, float density, uint64_t seed, const uint8_t* shared_map,
                    int32_t max_retries, void* obs, void* stream) {
-    if (!e || !env_mask) return fail(PGX_E_INVALID, "pgx_regenerate: null argument");
-    if (!e->has_state) return fail(PGX_E_STATE, "pgx_regenerate before the first reset");
+    if (!e || !env_mask) return fail_msg(PGX_E_INVALID, "pgx_regenerate: null argument");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_regenerate", true)) return rc;
     if (!shared_map && !(density >= 0.0f && density <= 1.0f))
-        return fail(PGX_E_INVALID, "density %.3f outside [0, 1]", (double)density);
+        return fail_msg(PGX_E_INVALID, "density %.3f outside [0, 1]", (double)density);
     if (max_retries < 1) max_retries = 3;
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
     if (int rc = ensure_reset_scratch(e, true)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const pgx_config& c = e->cfg;
@@ -518,10 +585,7 @@ int pgx_regenerate(pgx_env* e, const uint8_t* env_mask, float density, uint64_t 
     PGX_HIP(pgx::launch_reset_begin(env_mask, e->todo, e->regen, e->epoch, c.batch, s));
     PGX_HIP(pgx::launch_reset_env(p, s));
     if (obs) {
-        pgx::StepParams sp;
-        fill_params(e, sp);
-        sp.mode = pgx::MODE_OBSERVE;
-        sp.obs = static_cast<float*>(obs);
+        pgx::StepParams sp = observe_params(e, obs);
         sp.only = e->regen;
         PGX_HIP(pgx::launch_step(sp, e->geo, s));
     }
@@ -529,9 +593,8 @@ int pgx_regenerate(pgx_env* e, const uint8_t* env_mask, float density, uint64_t 
 }
 
 int64_t pgx_regenerate_failures(pgx_env* e, void* stream) {
-    if (!e) return fail(PGX_E_INVALID, "pgx_regenerate_failures: null handle");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_regenerate_failures", false)) return rc;
     uint32_t n = 0;
     PGX_HIP(hipMemcpyAsync(&n, e->regen_fail, sizeof n, hipMemcpyDeviceToHost, (hipStream_t)stream));
     PGX_HIP(hipStreamSynchronize((hipStream_t)stream));
@@ -591,10 +654,9 @@ int64_t pgx_snapshot_bytes(pgx_env* e) {
 }
 
 int pgx_save_snapshot(pgx_env* e, void* blob, void* stream) {
-    if (!e || !blob) return fail(PGX_E_INVALID, "pgx_save_snapshot: null argument");
-    if (!e->has_state) return fail(PGX_E_STATE, "pgx_save_snapshot called before a reset");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
+    if (!e || !blob) return fail_msg(PGX_E_INVALID, "pgx_save_snapshot: null argument");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_save_snapshot", true)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const SnapHeader header = snapshot_header(e, pgx_snapshot_bytes(e));
     PGX_HIP(hipMemcpyAsync(blob, &header, sizeof header, hipMemcpyHostToDevice, s));
@@ -608,23 +670,23 @@ int pgx_save_snapshot(pgx_env* e, void* blob, void* stream) {
 }
 
 int pgx_load_snapshot(pgx_env* e, const void* blob, void* stream) {
-    if (!e || !blob) return fail(PGX_E_INVALID, "pgx_load_snapshot: null argument");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
+    if (!e || !blob) return fail_msg(PGX_E_INVALID, "pgx_load_snapshot: null argument");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_load_snapshot", false)) return rc;
     hipStream_t s = (hipStream_t)stream;
     SnapHeader got{};
     PGX_HIP(hipMemcpyAsync(&got, blob, sizeof got, hipMemcpyDeviceToHost, s));
     PGX_HIP(hipStreamSynchronize(s));
     const SnapHeader want = snapshot_header(e, pgx_snapshot_bytes(e));
     if (memcmp(&got, &want, sizeof want) != 0)
-        return fail(PGX_E_INVALID,
-                    "snapshot does not belong to this configuration: blob has magic %08x abi %d batch %d agents %d map %dx%d "
-                    "r %d on_target %d collision %d max_steps %d bytes %lld; this handle abi %d batch %d agents %d map %dx%d "
-                    "r %d on_target %d collision %d max_steps %d bytes %lld",
-                    (unsigned)got.magic, got.abi, got.batch, got.num_agents, got.height, got.width, got.obs_radius,
-                    got.on_target, got.collision_system, got.max_episode_steps, (long long)got.total_bytes, want.abi,
-                    want.batch, want.num_agents, want.height, want.width, want.obs_radius, want.on_target,
-                    want.collision_system, want.max_episode_steps, (long long)want.total_bytes);
+        return fail_msg(PGX_E_INVALID,
+                        "snapshot does not belong to this configuration: blob has magic %08x abi %d batch %d agents %d map %dx%d "
+                        "r %d on_target %d collision %d max_steps %d bytes %lld; this handle abi %d batch %d agents %d map %dx%d "
+                        "r %d on_target %d collision %d max_steps %d bytes %lld",
+                        (unsigned)got.magic, got.abi, got.batch, got.num_agents, got.height, got.width, got.obs_radius,
+                        got.on_target, got.collision_system, got.max_episode_steps, (long long)got.total_bytes, want.abi,
+                        want.batch, want.num_agents, want.height, want.width, want.obs_radius, want.on_target,
+                        want.collision_system, want.max_episode_steps, (long long)want.total_bytes);
     size_t off = SNAP_HEADER_BYTES;
     for (const Segment& g : snapshot_segments(e)) {
         PGX_HIP(hipMemcpyAsync(g.ptr, (const char*)blob + off, g.bytes, hipMemcpyDeviceToDevice, s));
@@ -635,77 +697,21 @@ int pgx_load_snapshot(pgx_env* e, const void* blob, void* stream) {
 }
 
 int pgx_get_map(pgx_env* e, uint8_t* obstacles, void* stream) {
-    if (!e || !obstacles) return fail(PGX_E_INVALID, "pgx_get_map: null argument");
-    if (!e->has_state) return fail(PGX_E_STATE, "pgx_get_map called before a reset");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
+    if (!e || !obstacles) return fail_msg(PGX_E_INVALID, "pgx_get_map: null argument");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_get_map", true)) return rc;
     PGX_HIP(hipMemcpyAsync(obstacles, e->map_u8, (size_t)e->cfg.batch * e->cfg.height * e->cfg.width,
                            hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PGX_OK;
 }
 
-static void fill_params(const pgx_env* e, pgx::StepParams& p) {
-    const pgx_config& c = e->cfg;
-    memset(&p, 0, sizeof p);
-    p.batch = c.batch;
-    p.num_agents = c.num_agents;
-    p.r = c.obs_radius;
-    p.wpr = e->wpr;
-    p.bm_words = e->bmw;
-    p.map_w = c.width;
-    p.map_cells = c.height * c.width;
-    p.w_magic = (uint32_t)((1ull << 32) / (uint64_t)e->W) + 1u;
-    p.a_magic = c.num_agents > 1 ? (uint32_t)((1ull << 32) / (uint64_t)c.num_agents) + 1u : 0u;  // 0: A = 1, slot = env
-    p.collision = c.collision_system;
-    p.on_target = c.on_target;
-    p.max_steps = c.max_episode_steps;
-    p.auto_reset = c.auto_reset;
-    p.flags = e->flags;
-    p.epw = e->geo.epw;
-    p.stagger = e->geo.stagger;
-    p.store_policy = e->geo.store_policy;
-    p.state_stores = e->geo.state_stores;
-    for (int x = 0; x < 8; ++x) {
-        p.xcd_n[x] = e->geo.xcd_n[x];
-        p.xcd_base[x] = e->geo.xcd_base[x];
-    }
-    p.obs_u8 = e->cfg.obs_dtype == PGX_OBS_U8 ? 1 : 0;
-    p.obs_one = e->cfg.obs_dtype == PGX_OBS_BF16 ? 0x3F80u : e->cfg.obs_dtype == PGX_OBS_F16 ? 0x3C00u : 0u;
-    p.soft_rule = c.soft_vertex_rule;
-    p.soft_occupancy = c.soft_occupancy;
-    p.coop_reward = c.coop_reward;
-    p.bad_action = c.bad_action;
-    p.bad_count = e->bad_count;
-    p.seed = c.seed;
-    p.env_index_base = c.env_index_base;
-    p.obst = e->obst;
-    p.pos = e->pos;
-    p.tgt = e->tgt;
-    p.active = e->active;
-    p.elapsed = e->elapsed;
-    p.pos0 = e->pos0;
-    p.tgt0 = e->tgt0;
-    p.comp_begin = e->comp_begin;
-    p.comp_len = e->comp_len;
-    p.comp_cells = e->comp_cells;
-    p.tcount = e->tcount;
-    p.np_state = e->np_state;
-    p.np_state0 = e->np_state0;
-    p.dbg = e->dbg;
-    p.macc = e->macc;
-    p.metrics_out = e->metrics_out;
-    p.episode_done = e->episode_done;
-}
-
 int pgx_step(pgx_env* e, const void* actions, int action_dtype, void* obs, float* rewards, uint8_t* terminated,
              uint8_t* truncated, uint8_t* is_active, void* stream) {
-    if (!e || !actions || !rewards || !terminated || !truncated) return fail(PGX_E_INVALID, "pgx_step: null argument");
-    if (action_dtype < 0 || action_dtype > 2) return fail(PGX_E_INVALID, "pgx_step: bad action_dtype %d", action_dtype);
-    if (!e->has_state) return fail(PGX_E_STATE, "pgx_step called before pgx_reset_from_state");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
-    pgx::StepParams p;
-    fill_params(e, p);
+    if (!e || !actions || !rewards || !terminated || !truncated) return fail_msg(PGX_E_INVALID, "pgx_step: null argument");
+    if (action_dtype < 0 || action_dtype > 2) return fail_msg(PGX_E_INVALID, "pgx_step: bad action_dtype %d", action_dtype);
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_step", true)) return rc;
+    pgx::StepParams p = step_params(e, e->geo);
     p.mode = pgx::MODE_STEP;
     p.action_dtype = action_dtype;
     p.actions = actions;
@@ -720,17 +726,15 @@ int pgx_step(pgx_env* e, const void* actions, int action_dtype, void* obs, float
 
 int pgx_rollout(pgx_env* e, int32_t steps, const pgx_rollout_io* io, void* stream) {
     if (!e || !io || !io->rewards || !io->terminated || !io->truncated)
-        return fail(PGX_E_INVALID, "pgx_rollout: null argument");
+        return fail_msg(PGX_E_INVALID, "pgx_rollout: null argument");
     if (io->policy_step0 < 0 || io->policy_step0 > ((int64_t)1 << 40))
-        return fail(PGX_E_INVALID, "pgx_rollout: policy_step0 outside 0..2^40");
-    if (steps < 1) return fail(PGX_E_INVALID, "pgx_rollout: steps must be >= 1, got %d", steps);
-    if (io->action_dtype < 0 || io->action_dtype > 2) return fail(PGX_E_INVALID, "pgx_rollout: bad action_dtype %d", io->action_dtype);
-    if (io->obs && io->obs_slots < 1) return fail(PGX_E_INVALID, "pgx_rollout: obs given but obs_slots = %d", io->obs_slots);
-    if (!e->has_state) return fail(PGX_E_STATE, "pgx_rollout called before a reset");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
-    pgx::StepParams p;
-    fill_params(e, p);
+        return fail_msg(PGX_E_INVALID, "pgx_rollout: policy_step0 outside 0..2^40");
+    if (steps < 1) return fail_msg(PGX_E_INVALID, "pgx_rollout: steps must be >= 1, got %d", steps);
+    if (io->action_dtype < 0 || io->action_dtype > 2) return fail_msg(PGX_E_INVALID, "pgx_rollout: bad action_dtype %d", io->action_dtype);
+    if (io->obs && io->obs_slots < 1) return fail_msg(PGX_E_INVALID, "pgx_rollout: obs given but obs_slots = %d", io->obs_slots);
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_rollout", true)) return rc;
+    pgx::StepParams p = step_params(e, e->geo_roll);
     p.mode = pgx::MODE_STEP;
     p.action_dtype = io->action_dtype;
     p.actions = io->actions;
@@ -758,30 +762,21 @@ int pgx_rollout(pgx_env* e, int32_t steps, const pgx_rollout_io* io, void* strea
     rp.actions_out = io->actions ? nullptr : io->actions_out;
     if (io->obs && io->obs_slot_stride != 0) {
         if (io->obs_slot_stride < rp.obs_stride || (io->obs_slot_stride & 15) != 0)
-            return fail(PGX_E_INVALID, "pgx_rollout: obs_slot_stride %lld is smaller than one observation tensor (%lld bytes) or not a multiple of 16",
-                        (long long)io->obs_slot_stride, (long long)rp.obs_stride);
+            return fail_msg(PGX_E_INVALID, "pgx_rollout: obs_slot_stride %lld is smaller than one observation tensor (%lld bytes) or not a multiple of 16",
+                            (long long)io->obs_slot_stride, (long long)rp.obs_stride);
         rp.obs_stride = io->obs_slot_stride;
-    }
-    p.epw = e->geo_roll.epw;
-    p.stagger = e->geo_roll.stagger;
-    p.store_policy = e->geo_roll.store_policy;
-    p.state_stores = e->geo_roll.state_stores;
-    for (int x = 0; x < 8; ++x) {
-        p.xcd_n[x] = e->geo_roll.xcd_n[x];
-        p.xcd_base[x] = e->geo_roll.xcd_base[x];
     }
     PGX_HIP(pgx::launch_rollout(p, rp, e->geo_roll, (hipStream_t)stream));
     return PGX_OK;
 }
 
 int pgx_expert_actions(pgx_env* e, int32_t flags, void* actions, int32_t action_dtype, int32_t* distance, void* stream) {
-    if (!e || !actions) return fail(PGX_E_INVALID, "pgx_expert_actions: null argument");
+    if (!e || !actions) return fail_msg(PGX_E_INVALID, "pgx_expert_actions: null argument");
     if (action_dtype < 0 || action_dtype > 2)
-        return fail(PGX_E_INVALID, "pgx_expert_actions: bad action_dtype %d", action_dtype);
-    if (flags & ~PGX_EXPERT_AGENTS_AS_OBSTACLES) return fail(PGX_E_INVALID, "pgx_expert_actions: unknown flags 0x%x", flags);
-    if (!e->has_state) return fail(PGX_E_STATE, "pgx_expert_actions called before pgx_reset_from_state");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
+        return fail_msg(PGX_E_INVALID, "pgx_expert_actions: bad action_dtype %d", action_dtype);
+    if (flags & ~PGX_EXPERT_AGENTS_AS_OBSTACLES) return fail_msg(PGX_E_INVALID, "pgx_expert_actions: unknown flags 0x%x", flags);
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_expert_actions", true)) return rc;
     const bool with_agents = (flags & PGX_EXPERT_AGENTS_AS_OBSTACLES) != 0;
     const size_t occ_words = pgx::expert_occupancy_words(e->cfg.batch, e->cfg.height, e->cfg.width);
     if (with_agents && occ_words && !e->expert_occ) {
@@ -789,16 +784,13 @@ int pgx_expert_actions(pgx_env* e, int32_t flags, void* actions, int32_t action_
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         PGX_HIP(hipStreamIsCapturing((hipStream_t)stream, &cap));
         if (cap != hipStreamCaptureStatusNone)
-            return fail(PGX_E_STATE, "pgx_expert_actions: the first call with PGX_EXPERT_AGENTS_AS_OBSTACLES on maps wider or "
+            return fail_msg(PGX_E_STATE, "pgx_expert_actions: the first call with PGX_EXPERT_AGENTS_AS_OBSTACLES on maps wider or "
                                      "taller than 64 allocates %zu bytes of scratch; make it once outside graph capture",
-                        occ_words * sizeof(uint32_t));
-        const hipError_t err = hipMalloc((void**)&e->expert_occ, occ_words * sizeof(uint32_t));
-        if (err != hipSuccess) {
-            e->expert_occ = nullptr;
-            return fail(err == hipErrorOutOfMemory ? PGX_E_NOMEM : PGX_E_HIP,
-                        "pgx_expert_actions: occupancy scratch of %zu bytes: %s", occ_words * sizeof(uint32_t),
-                        hipGetErrorString(err));
-        }
+                            occ_words * sizeof(uint32_t));
+        const hipError_t err = e->expert_occ.alloc(occ_words * sizeof(uint32_t));
+        if (err != hipSuccess)
+            return fail_msg(alloc_code(err), "pgx_expert_actions: occupancy scratch of %zu bytes: %s",
+                            occ_words * sizeof(uint32_t), hipGetErrorString(err));
     }
     pgx::ExpertParams p{};
     p.batch = e->cfg.batch;
@@ -822,19 +814,17 @@ int pgx_expert_actions(pgx_env* e, int32_t flags, void* actions, int32_t action_
 }
 
 int pgx_set_targets(pgx_env* e, const int32_t* target_xy, const uint8_t* agent_mask, void* stream) {
-    if (!e || !target_xy) return fail(PGX_E_INVALID, "pgx_set_targets: null argument");
-    if (!e->has_state) return fail(PGX_E_STATE, "pgx_set_targets called before a reset");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
+    if (!e || !target_xy) return fail_msg(PGX_E_INVALID, "pgx_set_targets: null argument");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_set_targets", true)) return rc;
     PGX_HIP(pgx::launch_set_targets(target_xy, agent_mask, e->tgt, (size_t)e->cfg.batch * e->cfg.num_agents,
                                     e->cfg.obs_radius, (hipStream_t)stream));
     return PGX_OK;
 }
 
 int64_t pgx_bad_action_count(pgx_env* e, void* stream) {
-    if (!e) return fail(PGX_E_INVALID, "pgx_bad_action_count: null handle");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_bad_action_count", false)) return rc;
     hipStream_t s = (hipStream_t)stream;
     uint32_t n = 0;
     PGX_HIP(hipMemcpyAsync(&n, e->bad_count, sizeof n, hipMemcpyDeviceToHost, s));
@@ -844,22 +834,17 @@ int64_t pgx_bad_action_count(pgx_env* e, void* stream) {
 }
 
 int pgx_set_metrics_buffers(pgx_env* e, float* metrics, uint8_t* episode_done) {
-    if (!e) return fail(PGX_E_INVALID, "pgx_set_metrics_buffers: null handle");
+    if (!e) return fail_msg(PGX_E_INVALID, "pgx_set_metrics_buffers: null handle");
     e->metrics_out = metrics;
     e->episode_done = episode_done;
     return PGX_OK;
 }
 
 int pgx_observe(pgx_env* e, void* obs, void* stream) {
-    if (!e || !obs) return fail(PGX_E_INVALID, "pgx_observe: null argument");
-    if (!e->has_state) return fail(PGX_E_STATE, "pgx_observe called before pgx_reset_from_state");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
-    pgx::StepParams p;
-    fill_params(e, p);
-    p.mode = pgx::MODE_OBSERVE;
-    p.obs = static_cast<float*>(obs);
-    PGX_HIP(pgx::launch_step(p, e->geo, (hipStream_t)stream));
+    if (!e || !obs) return fail_msg(PGX_E_INVALID, "pgx_observe: null argument");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_observe", true)) return rc;
+    PGX_HIP(pgx::launch_step(observe_params(e, obs), e->geo, (hipStream_t)stream));
     return PGX_OK;
 }
 
@@ -868,74 +853,46 @@ int pgx_time_observe(pgx_env* e, void* obs, int32_t reps, float* microseconds, v
 }
 
 int pgx_time_observe_pair(pgx_env* e, void* obs, void* obs_alt, int32_t reps, float* microseconds, void* stream) {
-    if (!e || !obs || !microseconds) return fail(PGX_E_INVALID, "pgx_time_observe: null argument");
-    if (!e->has_state) return fail(PGX_E_STATE, "pgx_time_observe called before a reset");
+    if (!e || !obs || !microseconds) return fail_msg(PGX_E_INVALID, "pgx_time_observe: null argument");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_time_observe", true)) return rc;
     if (reps < 1) reps = 3;
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
-    hipStream_t s = (hipStream_t)stream;
-    pgx::StepParams p;
-    fill_params(e, p);
-    p.mode = pgx::MODE_OBSERVE;
-    p.obs = static_cast<float*>(obs);
-    hipEvent_t a, b;
-    PGX_HIP(hipEventCreate(&a));
-    PGX_HIP(hipEventCreate(&b));
-    float* const two[2] = {static_cast<float*>(obs), static_cast<float*>(obs_alt ? obs_alt : obs)};
-    for (int i = 0; i < (obs_alt ? 2 : 1); ++i) {  // warm-up: first touch of the buffer(s)
-        p.obs = two[i];
-        PGX_HIP(pgx::launch_step(p, e->geo, s));
-    }
-    PGX_HIP(hipEventRecord(a, s));
-    for (int i = 0; i < reps; ++i) {
-        p.obs = two[i & 1];
-        PGX_HIP(pgx::launch_step(p, e->geo, s));
-    }
-    PGX_HIP(hipEventRecord(b, s));
-    PGX_HIP(hipEventSynchronize(b));
-    float ms = 0.0f;
-    PGX_HIP(hipEventElapsedTime(&ms, a, b));
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    *microseconds = ms * 1000.0f / (float)reps;
+    // warm-up: first touch of the buffer(s)
+    void* const two[2] = {obs, obs_alt ? obs_alt : obs};
+    PGX_HIP(time_launches(observe_params(e, obs), e->geo, two, obs_alt ? 2 : 1, reps, (hipStream_t)stream, microseconds));
     return PGX_OK;
 }
 
 int pgx_xcd_tune(pgx_env* e, void* obs, void* obs_alt, int32_t rounds, float* us_equal, float* us_tuned, void* stream) {
-    if (!e || !obs) return fail(PGX_E_INVALID, "pgx_xcd_tune: null argument");
-    if (!e->has_state) return fail(PGX_E_STATE, "pgx_xcd_tune called before a reset");
+    if (!e || !obs) return fail_msg(PGX_E_INVALID, "pgx_xcd_tune: null argument");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_xcd_tune", true)) return rc;
     if (!e->xcd_aware) {  // not an 8-XCD SPX device: there are no per-XCD shares to tune (identity mapping)
         if (us_equal) *us_equal = 0.f;
         if (us_tuned) *us_tuned = 0.f;
         return PGX_OK;
     }
     if (rounds < 1) rounds = 6;
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
     hipStream_t s = (hipStream_t)stream;
     const int blocks = e->geo.multi_wave ? e->cfg.batch : (e->cfg.batch + e->geo.epw - 1) / e->geo.epw;
     const size_t nst = (size_t)blocks * 4;
-    unsigned long long* stamps = nullptr;
-    PGX_HIP(hipMalloc((void**)&stamps, nst * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> stamps;
+    PGX_HIP(stamps.alloc(nst * sizeof(unsigned long long)));
     std::vector<unsigned long long> host(nst);
-    hipEvent_t a = nullptr, b = nullptr;
-    hipError_t err = hipEventCreate(&a);
-    if (err == hipSuccess) err = hipEventCreate(&b);
+    void* const two[2] = {obs, obs_alt ? obs_alt : obs};
+    hipError_t err = hipSuccess;
     float best_w[8], w[8], best_us = 0.f, first_us = 0.f;
     for (int x = 0; x < 8; ++x) best_w[x] = w[x] = 0.125f;
-    for (int round = 0; round <= rounds && err == hipSuccess; ++round) {
+    for (int round = 0; round <= rounds; ++round) {
         for (int x = 0; x < 8; ++x) e->xcd_w[x] = w[x];
         apply_xcd_shares(e);
-        pgx::StepParams p;
-        fill_params(e, p);
-        p.mode = pgx::MODE_OBSERVE;
-        p.obs = static_cast<float*>(obs);
-        float* const two[2] = {static_cast<float*>(obs), static_cast<float*>(obs_alt ? obs_alt : obs)};
+        const pgx::StepParams p = observe_params(e, obs);
         // when each XCD is through with its share (per-workgroup end stamps of one launch) ...
+        pgx::StepParams stamped = p;
+        stamped.flags = (p.flags | 4u) & ~64u;
+        stamped.dbg = stamps;
         err = hipMemsetAsync(stamps, 0, nst * sizeof(unsigned long long), s);
-        p.flags = (p.flags | 4u) & ~64u;
-        p.dbg = stamps;
-        if (err == hipSuccess) err = pgx::launch_step(p, e->geo, s);
+        if (err == hipSuccess) err = pgx::launch_step(stamped, e->geo, s);
         if (err == hipSuccess) err = hipMemcpyAsync(host.data(), stamps, nst * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
         if (err == hipSuccess) err = hipStreamSynchronize(s);
         if (err != hipSuccess) break;
@@ -952,24 +909,9 @@ int pgx_xcd_tune(pgx_env* e, void* obs, void* obs_alt, int32_t rounds, float* us
         }
         // ... and how long the launch takes with these shares: alternating between the two buffers as pgx_step's caller
         // does, always after the same prelude (the stamped launch and its read-back), two passes to settle, eight timed
-        p.flags = e->flags;
-        p.dbg = e->dbg;
-        for (int i = 0; i < 2 && err == hipSuccess; ++i) {
-            p.obs = two[i & 1];
-            err = pgx::launch_step(p, e->geo, s);
-        }
-        if (err == hipSuccess) err = hipEventRecord(a, s);
-        const int timed = 8;
-        for (int i = 0; i < timed && err == hipSuccess; ++i) {
-            p.obs = two[i & 1];
-            err = pgx::launch_step(p, e->geo, s);
-        }
-        if (err == hipSuccess) err = hipEventRecord(b, s);
-        if (err == hipSuccess) err = hipEventSynchronize(b);
-        float ms = 0.f;
-        if (err == hipSuccess) err = hipEventElapsedTime(&ms, a, b);
+        float us = 0.f;
+        err = time_launches(p, e->geo, two, 2, 8, s, &us);
         if (err != hipSuccess) break;
-        const float us = ms * 1000.0f / (float)timed;
         if (round == 0) first_us = us;
         if (round == 0 || us < best_us) {
             best_us = us;
@@ -992,9 +934,6 @@ int pgx_xcd_tune(pgx_env* e, void* obs, void* obs_alt, int32_t rounds, float* us
     }
     for (int x = 0; x < 8; ++x) e->xcd_w[x] = best_w[x];
     apply_xcd_shares(e);
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-    (void)hipFree(stamps);
     PGX_HIP(err);
     if (us_equal) *us_equal = first_us;
     if (us_tuned) *us_tuned = best_us;
@@ -1003,10 +942,8 @@ int pgx_xcd_tune(pgx_env* e, void* obs, void* obs_alt, int32_t rounds, float* us
 
 int pgx_get_state(pgx_env* e, int32_t* agent_xy, int32_t* target_xy, uint8_t* is_active, int32_t* elapsed,
                   uint8_t* occupancy, void* stream) {
-    if (!e) return fail(PGX_E_INVALID, "pgx_get_state: null handle");
-    if (!e->has_state) return fail(PGX_E_STATE, "pgx_get_state called before pgx_reset_from_state");
-    DeviceGuard guard(e->device);
-    if (guard.err != hipSuccess) return fail(PGX_E_HIP, "cannot select device: %s", hipGetErrorString(guard.err));
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_get_state", true)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const pgx_config& c = e->cfg;
     const size_t B = (size_t)c.batch, BA = B * c.num_agents;
@@ -1023,13 +960,13 @@ int pgx_get_state(pgx_env* e, int32_t* agent_xy, int32_t* target_xy, uint8_t* is
 // Diagnostic only (not part of include/pogema_amd.h): copies the per-workgroup clock stamps of the last
 // launch to the host; needs PGX_FLAGS bit 2 at pgx_create.  Synchronises the device.
 int pgx_xcd_shares(pgx_env* e, int32_t* shares) {
-    if (!e || !shares) return fail(PGX_E_INVALID, "pgx_xcd_shares: null argument");
+    if (!e || !shares) return fail_msg(PGX_E_INVALID, "pgx_xcd_shares: null argument");
     for (int x = 0; x < 8; ++x) shares[x] = e->geo.xcd_n[x];
     return PGX_OK;
 }
 
 int pgx_get_geometry(const pgx_env* e, int32_t for_rollout, pgx_geometry* out) {
-    if (!e || !out) return fail(PGX_E_INVALID, "pgx_get_geometry: null argument");
+    if (!e || !out) return fail_msg(PGX_E_INVALID, "pgx_get_geometry: null argument");
     const pgx::StepGeometry& g = for_rollout ? e->geo_roll : e->geo;
     out->lanes_per_env = g.G;
     out->waves = g.waves * (g.pc ? 2 : 1);
@@ -1054,172 +991,14 @@ int pgx_get_geometry(const pgx_env* e, int32_t for_rollout, pgx_geometry* out) {
 }
 
 int pgx_debug_timestamps(pgx_env* e, unsigned long long* host_out, int64_t max_elems) {
-    if (!e || !host_out) return fail(PGX_E_INVALID, "pgx_debug_timestamps: null argument");
-    if (!e->dbg) return fail(PGX_E_STATE, "diagnostic stamps not enabled (PGX_FLAGS bit 2)");
-    DeviceGuard guard(e->device);
+    if (!e || !host_out) return fail_msg(PGX_E_INVALID, "pgx_debug_timestamps: null argument");
+    if (!e->dbg) return fail_msg(PGX_E_STATE, "diagnostic stamps not enabled (PGX_FLAGS bit 2)");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_debug_timestamps", false)) return rc;
     PGX_HIP(hipDeviceSynchronize());
     const size_t n = std::min<size_t>(e->dbg_elems, (size_t)max_elems);
     PGX_HIP(hipMemcpy(host_out, e->dbg, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return (int)PGX_OK;
-}
-
-// ================================================================================================
-// host-side synthetic generator
-// ================================================================================================
-namespace {
-
-// ---- instance generator "GEN v2" (host side) ---------------------------------------------------------
-// Counter-based so that the device kernels (pgx_reset_random) draw the very same instances:
-//   h = mix(seed, global env, epoch, attempt);  obstacle(c) <=> hash(h, 'OBST', c) >> 40 < thr;
-//   candidates c_t = hash(h, 'PLAC', t) scaled to [0, cells); first visit of a component opens a pair,
-//   the next visit closes it.  Normative statement: oracle/generator_oracle.py (test infrastructure).
-inline uint64_t sm64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-struct GenScratch {
-    std::vector<int32_t> label, stack, pending;
-    std::vector<uint8_t> taken;
-};
-
-void label_min_index(const uint8_t* obst, int H, int Wd, GenScratch& g) {
-    const int cells = H * Wd;
-    g.label.assign(cells, -1);
-    for (int s = 0; s < cells; ++s) {
-        if (obst[s] || g.label[s] >= 0) continue;
-        g.label[s] = s;  // row-major scan: the first cell reached is the component's smallest index
-        g.stack.clear();
-        g.stack.push_back(s);
-        while (!g.stack.empty()) {
-            const int c = g.stack.back();
-            g.stack.pop_back();
-            const int x = c / Wd, y = c - x * Wd;
-            const int nb[4] = {x > 0 ? c - Wd : -1, x + 1 < H ? c + Wd : -1, y > 0 ? c - 1 : -1, y + 1 < Wd ? c + 1 : -1};
-            for (int k = 0; k < 4; ++k) {
-                const int n = nb[k];
-                if (n >= 0 && !obst[n] && g.label[n] < 0) {
-                    g.label[n] = s;
-                    g.stack.push_back(n);
-                }
-            }
-        }
-    }
-}
-
-// one env, one attempt; returns true when `A` start/target pairs were placed
-// (obst_out == nullptr: place on the given `obst_in` map instead of drawing one; labels then reused)
-bool generate_one(int H, int Wd, int A, uint32_t thr, uint64_t h, const uint8_t* obst_in, uint8_t* obst_out,
-                  bool relabel, int32_t* axy, int32_t* txy, GenScratch& g) {
-    const int cells = H * Wd;
-    if (obst_out)
-        for (int c = 0; c < cells; ++c)
-            obst_out[c] = (sm64(h ^ (pgx::GEN_TAG_OBST | (uint64_t)c)) >> 40) < thr ? 1 : 0;
-    const uint8_t* obst = obst_out ? obst_out : obst_in;
-    if (relabel) label_min_index(obst, H, Wd, g);
-    g.taken.assign(cells, 0);
-    g.pending.assign(cells, -1);
-    int placed = 0;
-    const uint32_t budget = pgx::gen_candidate_budget((uint32_t)cells);
-    for (uint32_t t = 0; t < budget && placed < A; ++t) {
-        const uint32_t c = (uint32_t)(((sm64(h ^ (pgx::GEN_TAG_PLACE | (uint64_t)t)) >> 32) * (uint64_t)cells) >> 32);
-        if (obst[c] || g.taken[c]) continue;
-        g.taken[c] = 1;
-        int32_t& open = g.pending[g.label[c]];
-        if (open < 0) {
-            open = (int32_t)c;
-        } else {
-            axy[2 * placed] = open / Wd;
-            axy[2 * placed + 1] = open % Wd;
-            txy[2 * placed] = (int32_t)c / Wd;
-            txy[2 * placed + 1] = (int32_t)c % Wd;
-            open = -1;
-            ++placed;
-        }
-    }
-    return placed == A;
-}
-
-inline uint64_t instance_hash(uint64_t seed, uint64_t env, uint32_t epoch, uint32_t attempt) {
-    return sm64(sm64(sm64(seed) ^ env) ^ (((uint64_t)epoch << 32) | attempt));
-}
-
-}  // namespace
-
-int pgx_generate(int32_t batch, int32_t height, int32_t width, int32_t num_agents, float density, uint64_t seed0,
-                 int64_t env_index_base, int32_t max_retries, int32_t nthreads, uint8_t* obstacles, int32_t* agent_xy,
-                 int32_t* target_xy) {
-    if (batch < 1 || height < 1 || width < 1 || num_agents < 1 || !obstacles || !agent_xy || !target_xy)
-        return fail(PGX_E_INVALID, "pgx_generate: bad argument");
-    if (!(density >= 0.0f && density <= 1.0f)) return fail(PGX_E_INVALID, "density %.3f outside [0, 1]", (double)density);
-    if ((int64_t)2 * num_agents > (int64_t)height * width)
-        return fail(PGX_E_PLACEMENT, "%d agents need %d distinct cells, map has %d", num_agents, 2 * num_agents,
-                    height * width);
-    if (max_retries < 1) max_retries = 10;
-    const uint32_t thr = pgx::gen_density_threshold(density);
-    unsigned nt = nthreads > 0 ? (unsigned)nthreads : std::max(1u, std::thread::hardware_concurrency());
-    nt = (unsigned)std::min<int64_t>(nt, batch);
-    const size_t cells = (size_t)height * width;
-    std::vector<int> failed(nt, -1);
-    std::vector<std::thread> pool;
-    for (unsigned t = 0; t < nt; ++t) {
-        pool.emplace_back([&, t]() {
-            GenScratch g;
-            for (int64_t b = t; b < batch; b += nt) {
-                bool ok = false;
-                for (int attempt = 0; attempt < max_retries && !ok; ++attempt) {
-                    // env b of the call is global env (env_index_base + b) of stream `seed0`: shards and single-env
-                    // calls draw the same instances, and different seeds share none
-                    const uint64_t h = instance_hash(seed0, (uint64_t)(env_index_base + b), 0, (uint32_t)attempt);
-                    ok = generate_one(height, width, num_agents, thr, h, nullptr, obstacles + b * cells, true,
-                                      agent_xy + (size_t)b * num_agents * 2, target_xy + (size_t)b * num_agents * 2, g);
-                }
-                if (!ok && failed[t] < 0) failed[t] = (int)b;
-            }
-        });
-    }
-    for (auto& th : pool) th.join();
-    for (unsigned t = 0; t < nt; ++t)
-        if (failed[t] >= 0)
-            return fail(PGX_E_PLACEMENT, "could not place %d agents in env %d after %d attempts (density %.2f, %dx%d)",
-                        num_agents, failed[t], max_retries, (double)density, height, width);
-    return PGX_OK;
-}
-
-int pgx_place_agents(int32_t batch, int32_t height, int32_t width, int32_t num_agents, uint64_t seed0,
-                     int64_t env_index_base, int32_t max_retries, int32_t nthreads, const uint8_t* obstacles,
-                     int32_t shared_map, int32_t* agent_xy, int32_t* target_xy) {
-    if (batch < 1 || height < 1 || width < 1 || num_agents < 1 || !obstacles || !agent_xy || !target_xy)
-        return fail(PGX_E_INVALID, "pgx_place_agents: bad argument");
-    if (max_retries < 1) max_retries = 10;
-    unsigned nt = nthreads > 0 ? (unsigned)nthreads : std::max(1u, std::thread::hardware_concurrency());
-    nt = (unsigned)std::min<int64_t>(nt, batch);
-    const size_t cells = (size_t)height * width;
-    std::vector<int> failed(nt, -1);
-    std::vector<std::thread> pool;
-    for (unsigned t = 0; t < nt; ++t) {
-        pool.emplace_back([&, t]() {
-            GenScratch g;
-            for (int64_t b = t; b < batch; b += nt) {
-                bool ok = false;
-                const uint8_t* m = obstacles + (shared_map ? 0 : b * cells);
-                for (int attempt = 0; attempt < max_retries && !ok; ++attempt) {
-                    const uint64_t h = instance_hash(seed0, (uint64_t)(env_index_base + b), 0, (uint32_t)attempt);
-                    ok = generate_one(height, width, num_agents, 0u, h, m, nullptr, attempt == 0 || !shared_map,
-                                      agent_xy + (size_t)b * num_agents * 2, target_xy + (size_t)b * num_agents * 2, g);
-                }
-                if (!ok && failed[t] < 0) failed[t] = (int)b;
-            }
-        });
-    }
-    for (auto& th : pool) th.join();
-    for (unsigned t = 0; t < nt; ++t)
-        if (failed[t] >= 0)
-            return fail(PGX_E_PLACEMENT, "could not place %d agents on the given map of env %d after %d attempts",
-                        num_agents, failed[t], max_retries);
-    return PGX_OK;
 }
 
 }  // extern "C"

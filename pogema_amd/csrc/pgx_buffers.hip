@@ -27,10 +27,9 @@
 #include <vector>
 
 #include "../../include/pogema_amd.h"
+#include "pgx_internal.h"
 
 namespace pgx {
-// defined in pgx_api.cpp
-int fail_msg(int code, const char* fmt, ...);
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -409,14 +408,10 @@ int pgx_buffers_create_at(int device, size_t bytes, int count, double skip_gib, 
     if (!out) return pgx::fail_msg(PGX_E_INVALID, "pgx_buffers_create: null argument");
     *out = nullptr;
     if (bytes == 0 || count < 1 || count > 64) return pgx::fail_msg(PGX_E_INVALID, "pgx_buffers_create: bad size or count");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess)
-        return pgx::fail_msg(PGX_E_HIP, "cannot select HIP device %d", device);
+    pgx::DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return pgx::fail_msg(PGX_E_HIP, "cannot select HIP device %d", device);
     pgx_buffers* p = new (std::nothrow) pgx_buffers();
-    if (!p) {
-        (void)hipSetDevice(prev);
-        return pgx::fail_msg(PGX_E_NOMEM, "out of host memory");
-    }
+    if (!p) return pgx::fail_msg(PGX_E_NOMEM, "out of host memory");
     p->device = device;
     p->bytes = bytes;
     p->count = count;
@@ -432,7 +427,6 @@ int pgx_buffers_create_at(int device, size_t bytes, int count, double skip_gib, 
         for (Range& s : held) s.release();
         destroy(p);
         (void)hipGetLastError();
-        (void)hipSetDevice(prev);
         return pgx::fail_msg(code, "%s", msg.c_str());
     };
     auto code_of = [](hipError_t e) { return e == hipErrorOutOfMemory ? PGX_E_NOMEM : PGX_E_HIP; };
@@ -488,7 +482,6 @@ int pgx_buffers_create_at(int device, size_t bytes, int count, double skip_gib, 
     }
     (void)hipGetLastError();
     *out = p;
-    (void)hipSetDevice(prev);
     return PGX_OK;
 }
 
@@ -501,13 +494,10 @@ int64_t pgx_buffers_stride(pgx_buffers* p) { return p ? (int64_t)p->stride : 0; 
 
 int pgx_buffers_drop(pgx_buffers* p, int index) {
     if (!p || index < 0 || index >= p->count) return pgx::fail_msg(PGX_E_INVALID, "pgx_buffers_drop: bad argument");
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(p->device);
+    pgx::DeviceGuard guard(p->device);
     (void)hipDeviceSynchronize();  // nothing may still be writing into the buffer
     drop_part(p->all.parts[(size_t)2 * index]);
     drop_part(p->all.parts[(size_t)2 * index + 1]);
-    if (prev >= 0) (void)hipSetDevice(prev);
     return PGX_OK;
 }
 
@@ -524,12 +514,9 @@ int64_t pgx_buffers_va_reserved(void) {
 
 int pgx_buffers_destroy(pgx_buffers* p) {
     if (!p) return PGX_OK;
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(p->device);
+    pgx::DeviceGuard guard(p->device);
     (void)hipDeviceSynchronize();  // nothing may still be writing into the ranges that are about to be unmapped
     destroy(p);
-    if (prev >= 0) (void)hipSetDevice(prev);
     return PGX_OK;
 }
 

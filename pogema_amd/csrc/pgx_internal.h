@@ -1,10 +1,45 @@
-// pgx_internal.h -- shared between pgx_kernels.hip (device code + launchers) and pgx_api.cpp (C-ABI).
+// pgx_internal.h -- shared by the library's translation units: device code + launchers (pgx_*.hip), the C-ABI
+// (pgx_api.cpp) and the host generator (pgx_generate.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 namespace pgx {
+
+// ---- host side of the C-ABI translation units ----
+// formats the message pgx_last_error() returns and passes `code` through (pgx_api.cpp)
+int fail_msg(int code, const char* fmt, ...);
+
+// makes `call` (a hipError_t expression) the entry point's result when it fails (PGX_E_HIP: include/pogema_amd.h)
+#define PGX_HIP(call)                                                                                                      \
+    do {                                                                                                                   \
+        const hipError_t e__ = (call);                                                                                     \
+        if (e__ != hipSuccess)                                                                                             \
+            return pgx::fail_msg(PGX_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
+    } while (0)
+
+// selects a device for the rest of the scope and restores the caller's on exit
+struct DeviceGuard {
+    int prev = -1;
+    bool changed = false;
+    hipError_t err = hipSuccess;
+    DeviceGuard() = default;
+    explicit DeviceGuard(int dev) { (void)select(dev); }
+    DeviceGuard(const DeviceGuard&) = delete;
+    DeviceGuard& operator=(const DeviceGuard&) = delete;
+    hipError_t select(int dev) {
+        err = hipGetDevice(&prev);
+        if (err == hipSuccess && prev != dev) {
+            err = hipSetDevice(dev);
+            changed = (err == hipSuccess);
+        }
+        return err;
+    }
+    ~DeviceGuard() {
+        if (changed) (void)hipSetDevice(prev);
+    }
+};
 
 enum { MODE_STEP = 0, MODE_OBSERVE = 1 };
 enum { COLLISION_PRIORITY = 0, COLLISION_BLOCK_BOTH = 1, COLLISION_SOFT = 2 };
@@ -33,11 +68,17 @@ struct OutsideParams {
     int64_t env_index_base;
     const uint32_t* epoch;   // [B] generation counters
 };
-__host__ __device__ inline uint64_t gen_sm64(uint64_t z) {
+// splitmix64: the one hash of every counter-based stream of the library (instances, lifelong targets, random policy)
+__host__ __device__ __forceinline__ uint64_t gen_sm64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
+}
+// the key of one generator attempt; host (pgx_generate) and device (pgx_reset_random) must draw the same instances.
+// Seed and global env index are separate key components: adjacent seeds share no instance.
+__host__ __device__ __forceinline__ uint64_t gen_instance_hash(uint64_t seed, uint64_t env, uint32_t epoch, uint32_t attempt) {
+    return gen_sm64(gen_sm64(gen_sm64(seed) ^ env) ^ (((uint64_t)epoch << 32) | attempt));
 }
 // is padded cell (x, y) beyond the ring? (the ring itself and the map interior are never "outside")
 __host__ __device__ inline bool gen_is_outside(int x, int y, int PH, int PW, int r) {

@@ -34,28 +34,21 @@
 
 namespace pgx {
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // docs/SPEC.md S5, lifelong stream: uniform index in [0, n) for (seed, global env, agent, counter).
 __device__ __forceinline__ uint32_t lifelong_draw(uint64_t seed, uint64_t env_index, uint32_t agent,
                                                   uint32_t counter, uint32_t n) {
-    uint64_t h = splitmix64(seed);
-    h = splitmix64(h ^ env_index);
-    h = splitmix64(h ^ (((uint64_t)agent << 32) | counter));
+    uint64_t h = gen_sm64(seed);
+    h = gen_sm64(h ^ env_index);
+    h = gen_sm64(h ^ (((uint64_t)agent << 32) | counter));
     return (uint32_t)(((h >> 32) * (uint64_t)n) >> 32);
 }
 
 // pgx_rollout without an action tensor: the uniform random policy, action in 0..4 for (seed, global env, agent, step).
 // Stated in oracle/generator_oracle.py (policy_action); tests/test_rollout_gpu.py.
 __device__ __forceinline__ int policy_action(uint64_t seed, uint64_t env_index, uint32_t agent, uint64_t step) {
-    uint64_t h = splitmix64(seed ^ 0x504F4C4943590000ull);  // 'POLICY'
-    h = splitmix64(h ^ env_index);
-    h = splitmix64(h ^ (step << 20 | (uint64_t)agent));
+    uint64_t h = gen_sm64(seed ^ 0x504F4C4943590000ull);  // 'POLICY'
+    h = gen_sm64(h ^ env_index);
+    h = gen_sm64(h ^ (step << 20 | (uint64_t)agent));
     return (int)(((h >> 32) * 5ull) >> 32);
 }
 

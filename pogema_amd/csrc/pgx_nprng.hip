@@ -6,10 +6,10 @@
 #include <vector>
 
 #include "../../include/pogema_amd.h"
+#include "pgx_internal.h"
 #include "pgx_nprng.h"
 
 namespace pgx {
-int fail_msg(int code, const char* fmt, ...);
 
 __host__ __device__ inline void np_stream_run(uint64_t seed, int op, uint64_t n, double p, double qn, int64_t draws, void* out_row) {
     pgxnp::Pcg64 g = pgxnp::default_rng(seed);

@@ -25,18 +25,6 @@ namespace pgx {
 
 namespace {
 
-__device__ __forceinline__ uint64_t sm64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// seed and global env index are separate key components: adjacent seeds share no instance
-__device__ __forceinline__ uint64_t instance_hash(uint64_t seed, uint64_t env, uint32_t epoch, uint32_t attempt) {
-    return sm64(sm64(sm64(seed) ^ env) ^ (((uint64_t)epoch << 32) | attempt));
-}
-
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint32_t TAKEN = 0x80000000u;
 
@@ -154,7 +142,7 @@ __device__ int place_phase(const uint8_t* __restrict__ obst, const uint32_t* __r
     uint32_t cur_root = NONE, cur_val = 0u;  // cached pending word (wave-uniform)
     for (uint32_t t0 = 0; t0 < budget && placed < A; t0 += 64) {
         const uint32_t t = t0 + (uint32_t)lane;
-        const uint32_t c = (uint32_t)(((sm64(h ^ (GEN_TAG_PLACE | (uint64_t)t)) >> 32) * (uint64_t)cells) >> 32);
+        const uint32_t c = (uint32_t)(((gen_sm64(h ^ (GEN_TAG_PLACE | (uint64_t)t)) >> 32) * (uint64_t)cells) >> 32);
         const uint8_t blocked = obst[c];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the previous batch's marks have reached L2
         const uint32_t mark = ld<false>(pend + c);
@@ -378,12 +366,12 @@ __global__ __launch_bounds__(256) void reset_env_kernel(const ResetParams p) {
         const uint32_t epoch = p.epoch[env];
         bool ok = false;
         for (int attempt = 0; attempt < p.max_retries && !ok; ++attempt) {
-            const uint64_t h = instance_hash(p.gen_seed, (uint64_t)(p.env_index_base + env), epoch, (uint32_t)attempt);
+            const uint64_t h = gen_instance_hash(p.gen_seed, (uint64_t)(p.env_index_base + env), epoch, (uint32_t)attempt);
             const bool redraw = !p.shared_map || attempt == 0;
             for (int c = tid; c < cells; c += 256) {
                 if (redraw)
                     draft[c] = p.shared_map ? (p.shared_map[c] != 0 ? 1 : 0)
-                                            : ((sm64(h ^ (GEN_TAG_OBST | (uint64_t)c)) >> 40) < p.thr ? 1 : 0);
+                                            : ((gen_sm64(h ^ (GEN_TAG_OBST | (uint64_t)c)) >> 40) < p.thr ? 1 : 0);
                 st<false>(pend + c, 0u);
             }
             __syncthreads();
