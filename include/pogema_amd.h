@@ -204,6 +204,33 @@ int pgx_regenerate(pgx_env* env, const uint8_t* env_mask, float density, uint64_
                    int32_t max_retries, void* obs, void* stream);
 int64_t pgx_regenerate_failures(pgx_env* env, void* stream);
 
+/* ---- map pool (docs/SPEC.md S10) ----------------------------------------------------------------------------- */
+/* A pool is num_maps >= 1 maps of the handle's height x width, nonzero = obstacle.  With a pool installed,
+ * pgx_reset_pool / pgx_regenerate_pool give env i (global index e = env_index_base + i, generation `epoch`) the map
+ *   k = ((splitmix64(h0 ^ 0x504F4F4C00000000) >> 32) * num_maps) >> 32,   h0 = GEN v2's key of attempt 0
+ * and place its agents on pool[k] exactly as pgx_reset_random does on a shared map.  The map choice depends on
+ * (seed, e, epoch) only, so shards draw the same instances as one handle.
+ *
+ * pgx_set_map_pool copies `maps` (device u8 [num_maps, height, width]) into the handle, labels the components of every
+ * map once and checks that each can hold num_agents start/target pairs (sum over its components of floor(size / 2)):
+ * otherwise PGX_E_PLACEMENT naming the first such map, and no pool is installed.  `capacity_out` (host i32 [num_maps],
+ * may be NULL) receives every map's capacity.  It synchronises `stream` once to read the capacities and is refused
+ * (PGX_E_STATE) inside a graph capture.  A pool of the same num_maps reuses the handle's buffers (stream-ordered copy,
+ * so a graph captured over pgx_regenerate_pool draws from the new pool); another size synchronises the device and
+ * reallocates.  Current instances are kept until each env's next reset.  Device memory: 5 bytes per cell and map.
+ * map_index (pgx_get_map_index, device i32 [batch]) is the pool index of each env's map, -1 after any other install
+ * (pgx_reset_from_state, pgx_reset_random, pgx_regenerate, a snapshot taken without a pool) or before any pool.
+ * A handle with a pool installed appends map_index to its snapshot (pgx_snapshot_bytes grows by the aligned size). */
+int pgx_set_map_pool(pgx_env* env, const uint8_t* maps, int32_t num_maps, int32_t* capacity_out, void* stream);
+/* pgx_reset_random on the pool: env_mask, max_retries (<= 0: 10), the generation counters, the status and the one
+ * synchronisation are those of pgx_reset_random.  PGX_E_STATE without a pool. */
+int pgx_reset_pool(pgx_env* env, uint64_t seed, const uint8_t* env_mask, int32_t max_retries, void* stream);
+/* pgx_regenerate on the pool: asynchronous, no host sync; failures (max_retries <= 0: 3) keep the previous instance and
+ * are counted by pgx_regenerate_failures.  Needs 4 bytes of scratch per cell and env (allocated on first use). */
+int pgx_regenerate_pool(pgx_env* env, const uint8_t* env_mask, uint64_t seed, int32_t max_retries, void* obs,
+                        void* stream);
+int pgx_get_map_index(pgx_env* env, int32_t* map_index, void* stream);
+
 /* The unpadded obstacle maps currently installed: device u8 [batch, height, width] (`Grid.get_obstacles`). */
 int pgx_get_map(pgx_env* env, uint8_t* obstacles, void* stream);
 

@@ -62,7 +62,7 @@ EXPORTED_SYMBOLS = (
     "pgx_snapshot_bytes", "pgx_save_snapshot", "pgx_load_snapshot", "pgx_time_observe", "pgx_bad_action_count",
     "pgx_buffers_create", "pgx_buffers_ptr", "pgx_buffers_get_info", "pgx_buffers_destroy", "pgx_set_targets",
     "pgx_np_streams", "pgx_np_streams_host", "pgx_np_generate", "pgx_np_generate_host", "pgx_rollout", "pgx_buffers_stride", "pgx_buffers_drop", "pgx_xcd_shares", "pgx_xcd_tune", "pgx_buffers_create_at", "pgx_time_observe_pair", "pgx_buffers_va_reserved", "pgx_get_geometry",
-    "pgx_expert_actions",
+    "pgx_expert_actions", "pgx_set_map_pool", "pgx_reset_pool", "pgx_regenerate_pool", "pgx_get_map_index",
 )
 
 
@@ -172,6 +172,14 @@ def load() -> C.CDLL:
     lib.pgx_rollout.restype = C.c_int
     lib.pgx_expert_actions.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.pgx_expert_actions.restype = C.c_int
+    lib.pgx_set_map_pool.argtypes = [vp, vp, i32, vp, vp]
+    lib.pgx_set_map_pool.restype = C.c_int
+    lib.pgx_reset_pool.argtypes = [vp, u64, vp, i32, vp]
+    lib.pgx_reset_pool.restype = C.c_int
+    lib.pgx_regenerate_pool.argtypes = [vp, vp, u64, i32, vp, vp]
+    lib.pgx_regenerate_pool.restype = C.c_int
+    lib.pgx_get_map_index.argtypes = [vp, vp, vp]
+    lib.pgx_get_map_index.restype = C.c_int
     lib.pgx_set_targets.argtypes = [vp, vp, vp, vp]
     lib.pgx_set_targets.restype = C.c_int
     lib.pgx_bad_action_count.argtypes = [vp, vp]

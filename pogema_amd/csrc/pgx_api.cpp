@@ -95,8 +95,14 @@ struct pgx_env {
     DevBuf<uint32_t> expert_occ;          // [B][H][ceil(W/32)] occupancy bits of pgx_expert_actions' large-map layout
                                           // (allocated by its first call with agents as obstacles)
     DevBuf<uint32_t> labels, pending;     // [chunk_envs][H*W], allocated on first use
-    DevBuf<uint8_t> scratch_map;          // [chunk_envs][H*W] draft maps
+    DevBuf<uint8_t> scratch_map;          // [chunk_envs][H*W] draft maps (not allocated for pool-only resets)
     int chunk_envs = 0;
+    // map pool (pgx_set_map_pool): 5 bytes per cell and pool map
+    int pool_size = 0;                    // M (0: no pool installed)
+    DevBuf<uint8_t> pool_maps;            // [M][H*W] 0/1
+    DevBuf<uint32_t> pool_labels;         // [M][H*W] min-index component labels
+    DevBuf<uint32_t> pool_cap;            // [M] start/target pairs each map can hold
+    DevBuf<int32_t> map_index;            // [B] pool index of each env's map, -1 after a non-pool install
 };
 
 namespace {
@@ -428,36 +434,39 @@ int64_t pgx_agent_elems(const pgx_env* e) {
 }
 
 // ---- reset path ---------------------------------------------------------------------------------------
-// Scratch of the reset kernel: 9 bytes per cell and slot (draft map, labels, pending).  The synchronous resets
-// walk the batch in chunks of <= 2^25 cells' worth of environments (<= 288 MiB); pgx_regenerate, which must not
-// return to the host between chunks, wants one slot per environment (`full`).
-static int ensure_reset_scratch(pgx_env* e, bool full) {
+// Scratch of the reset kernel: 9 bytes per cell and slot (draft map, labels, pending); the pool kernels need the
+// pending words only (`pool`: 4 bytes).  The synchronous resets walk the batch in chunks of <= 2^25 cells' worth of
+// environments (<= 288 MiB); pgx_regenerate, which must not return to the host between chunks, wants one slot per
+// environment (`full`).
+static int ensure_reset_scratch(pgx_env* e, bool full, bool pool = false) {
     const size_t cells = (size_t)e->cfg.height * e->cfg.width;
+    const size_t per_cell = pool ? 4 : 9;
     size_t chunk = ((size_t)1 << 25) / cells;
     chunk = std::max<size_t>(1, std::min<size_t>(chunk, (size_t)e->cfg.batch));
     if (full) {
         chunk = (size_t)e->cfg.batch;
-        if (chunk * cells * 9 > ((size_t)32 << 30))
-            return fail_msg(PGX_E_NOMEM, "pgx_regenerate needs %zu bytes of scratch (9 per cell and env); use pgx_reset_random",
-                            chunk * cells * 9);
+        if (chunk * cells * per_cell > ((size_t)32 << 30))
+            return fail_msg(PGX_E_NOMEM, "%s needs %zu bytes of scratch (%zu per cell and env); use %s",
+                            pool ? "pgx_regenerate_pool" : "pgx_regenerate", chunk * cells * per_cell, per_cell,
+                            pool ? "pgx_reset_pool" : "pgx_reset_random");
     }
-    if (e->labels && (size_t)e->chunk_envs >= chunk) return PGX_OK;
+    if (e->pending && (size_t)e->chunk_envs >= chunk && (pool || e->labels)) return PGX_OK;
     auto release = [e]() {
         e->labels.reset();
         e->pending.reset();
         e->scratch_map.reset();
     };
-    if (e->labels) {
+    if (e->pending) {
         PGX_HIP(hipDeviceSynchronize());
         release();
     }
     e->chunk_envs = 0;
-    hipError_t err = e->labels.alloc(chunk * cells * sizeof(uint32_t));
-    if (err == hipSuccess) err = e->pending.alloc(chunk * cells * sizeof(uint32_t));
-    if (err == hipSuccess) err = e->scratch_map.alloc(chunk * cells);
+    hipError_t err = e->pending.alloc(chunk * cells * sizeof(uint32_t));
+    if (err == hipSuccess && !pool) err = e->labels.alloc(chunk * cells * sizeof(uint32_t));
+    if (err == hipSuccess && !pool) err = e->scratch_map.alloc(chunk * cells);
     if (err != hipSuccess) {  // all or nothing: a later call must not find half of the scratch
         release();
-        return fail_msg(alloc_code(err), "reset scratch (%zu bytes): %s", chunk * cells * 9, hipGetErrorString(err));
+        return fail_msg(alloc_code(err), "reset scratch (%zu bytes): %s", chunk * cells * per_cell, hipGetErrorString(err));
     }
     e->chunk_envs = (int)chunk;
     return PGX_OK;
@@ -508,6 +517,7 @@ int pgx_reset_from_state(pgx_env* e, const uint8_t* obstacles, const int32_t* ag
                                     c.obs_radius, s, e->np_state, e->np_state0));
     PGX_HIP(pgx::launch_zero_i32(e->elapsed, B, s));
     PGX_HIP(pgx::launch_zero_i32(reinterpret_cast<int32_t*>(e->macc.p), B * 4, s));
+    if (e->map_index) PGX_HIP(hipMemsetAsync(e->map_index, 0xFF, B * sizeof(int32_t), s));
     if (c.on_target == PGX_ON_TARGET_RESTART) {  // component tables of PogemaLifeLong, built on the device
         if (int rc = ensure_reset_scratch(e, false)) return rc;
         pgx::ResetParams p = reset_params(e);
@@ -550,6 +560,7 @@ int pgx_reset_random(pgx_env* e, float density, uint64_t seed, const uint8_t* sh
         p.env_count = std::min(e->chunk_envs, c.batch - b0);
         PGX_HIP(pgx::launch_reset_env(p, s));
     }
+    if (e->map_index) PGX_HIP(pgx::launch_clear_map_index(e->regen, e->todo, e->map_index, c.batch, s));
     uint32_t failed = 0;
     PGX_HIP(hipMemcpyAsync(&failed, e->fail_count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     PGX_HIP(hipStreamSynchronize(s));  // the status is the device's failure count
@@ -584,6 +595,7 @@ int pgx_regenerate(pgx_env* e, const uint8_t* env_mask, float density, uint64_t 
     p.env_count = c.batch;
     PGX_HIP(pgx::launch_reset_begin(env_mask, e->todo, e->regen, e->epoch, c.batch, s));
     PGX_HIP(pgx::launch_reset_env(p, s));
+    if (e->map_index) PGX_HIP(pgx::launch_clear_map_index(e->regen, e->todo, e->map_index, c.batch, s));
     if (obs) {
         pgx::StepParams sp = observe_params(e, obs);
         sp.only = e->regen;
@@ -601,6 +613,139 @@ int64_t pgx_regenerate_failures(pgx_env* e, void* stream) {
     return (int64_t)n;
 }
 
+// ---- map pool (docs/SPEC.md S10) ------------------------------------------------------------------------
+int pgx_set_map_pool(pgx_env* e, const uint8_t* maps, int32_t num_maps, int32_t* capacity_out, void* stream) {
+    if (!e || !maps) return fail_msg(PGX_E_INVALID, "pgx_set_map_pool: null argument");
+    if (num_maps < 1) return fail_msg(PGX_E_INVALID, "pgx_set_map_pool: num_maps must be >= 1, got %d", num_maps);
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_set_map_pool", false)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    PGX_HIP(hipStreamIsCapturing(s, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return fail_msg(PGX_E_STATE, "pgx_set_map_pool: the install check reads each map's capacity on the host; install "
+                                     "the pool outside graph capture (a same-size pool keeps its buffers, so a captured "
+                                     "graph sees it)");
+    const pgx_config& c = e->cfg;
+    const size_t cells = (size_t)c.height * c.width, M = (size_t)num_maps;
+    if (int rc = ensure_reset_scratch(e, false, true)) return rc;
+    if (num_maps != e->pool_size) {
+        // work already queued may still read the old pool: it finishes before the buffers go
+        PGX_HIP(hipDeviceSynchronize());
+        e->pool_size = 0;
+        hipError_t err = e->pool_maps.alloc(M * cells);
+        if (err == hipSuccess) err = e->pool_labels.alloc(M * cells * sizeof(uint32_t));
+        if (err == hipSuccess) err = e->pool_cap.alloc(M * sizeof(uint32_t));
+        if (err == hipSuccess && !e->map_index) {
+            err = e->map_index.alloc((size_t)c.batch * sizeof(int32_t));
+            if (err == hipSuccess) err = hipMemsetAsync(e->map_index, 0xFF, (size_t)c.batch * sizeof(int32_t), s);
+        }
+        if (err != hipSuccess) {
+            e->pool_maps.reset();
+            e->pool_labels.reset();
+            e->pool_cap.reset();
+            return fail_msg(alloc_code(err), "pgx_set_map_pool: %zu bytes for %d maps of %dx%d: %s", M * cells * 5 + M * 4,
+                            num_maps, c.height, c.width, hipGetErrorString(err));
+        }
+    }
+    for (size_t m0 = 0; m0 < M; m0 += (size_t)e->chunk_envs) {
+        const int count = (int)std::min<size_t>((size_t)e->chunk_envs, M - m0);
+        PGX_HIP(pgx::launch_pool_label(maps + m0 * cells, e->pool_maps + m0 * cells, e->pool_labels + m0 * cells, e->pending,
+                                       e->pool_cap + m0, count, c.height, c.width, s));
+    }
+    e->pool_size = num_maps;
+    std::vector<uint32_t> capacity(M);
+    PGX_HIP(hipMemcpyAsync(capacity.data(), e->pool_cap, M * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    PGX_HIP(hipStreamSynchronize(s));
+    if (capacity_out)
+        for (size_t m = 0; m < M; ++m) capacity_out[m] = (int32_t)capacity[m];
+    for (size_t m = 0; m < M; ++m)
+        if ((int64_t)capacity[m] < (int64_t)c.num_agents) {
+            // the refused pool is not installed (nor is the one it replaced): the envs keep their current instances
+            e->pool_size = 0;
+            return fail_msg(PGX_E_PLACEMENT, "pgx_set_map_pool: map %zu of the pool holds %u start/target pairs, %d agents "
+                                             "need %d (each pair lies in one connected component)",
+                            m, capacity[m], c.num_agents, c.num_agents);
+        }
+    return PGX_OK;
+}
+
+static pgx::ResetParams pool_reset_params(const pgx_env* e, uint64_t seed, int32_t max_retries) {
+    pgx::ResetParams p = reset_params(e);
+    p.max_retries = max_retries;
+    p.gen_seed = seed;
+    p.env_index_base = e->cfg.env_index_base;
+    p.pool_size = e->pool_size;
+    p.pool_maps = e->pool_maps;
+    p.pool_labels = e->pool_labels;
+    p.map_index = e->map_index;
+    return p;
+}
+
+int pgx_reset_pool(pgx_env* e, uint64_t seed, const uint8_t* env_mask, int32_t max_retries, void* stream) {
+    if (!e) return fail_msg(PGX_E_INVALID, "pgx_reset_pool: null handle");
+    if (!e->pool_size) return fail_msg(PGX_E_STATE, "pgx_reset_pool: no map pool installed (pgx_set_map_pool)");
+    if (env_mask && !e->has_state) return fail_msg(PGX_E_STATE, "masked pgx_reset_pool before the first full reset");
+    const pgx_config& c = e->cfg;
+    if (max_retries < 1) max_retries = 10;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_reset_pool", false)) return rc;
+    if (int rc = ensure_reset_scratch(e, false, true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::ResetParams p = pool_reset_params(e, seed, max_retries);
+    PGX_HIP(pgx::launch_reset_begin(env_mask, e->todo, e->regen, e->epoch, c.batch, s));
+    PGX_HIP(hipMemsetAsync(e->fail_count, 0, sizeof(uint32_t), s));
+    for (int b0 = 0; b0 < c.batch; b0 += e->chunk_envs) {
+        p.env_begin = b0;
+        p.env_count = std::min(e->chunk_envs, c.batch - b0);
+        PGX_HIP(pgx::launch_reset_pool(p, s));
+    }
+    uint32_t failed = 0;
+    PGX_HIP(hipMemcpyAsync(&failed, e->fail_count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    PGX_HIP(hipStreamSynchronize(s));  // the status is the device's failure count
+    if (failed) {
+        if (!env_mask) e->has_state = false;  // (masked: the failed envs keep their previous instance)
+        return fail_msg(PGX_E_PLACEMENT, "could not place %d agents in %u environment(s) after %d attempts on maps of the "
+                                         "pool (%d maps of %dx%d)",
+                        c.num_agents, failed, max_retries, e->pool_size, c.height, c.width);
+    }
+    e->has_state = true;
+    return PGX_OK;
+}
+
+int pgx_regenerate_pool(pgx_env* e, const uint8_t* env_mask, uint64_t seed, int32_t max_retries, void* obs, void* stream) {
+    if (!e || !env_mask) return fail_msg(PGX_E_INVALID, "pgx_regenerate_pool: null argument");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_regenerate_pool", true)) return rc;
+    if (!e->pool_size) return fail_msg(PGX_E_STATE, "pgx_regenerate_pool: no map pool installed (pgx_set_map_pool)");
+    if (max_retries < 1) max_retries = 3;
+    if (int rc = ensure_reset_scratch(e, true, true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const pgx_config& c = e->cfg;
+    pgx::ResetParams p = pool_reset_params(e, seed, max_retries);
+    p.fail_count = e->regen_fail;
+    p.env_begin = 0;
+    p.env_count = c.batch;
+    PGX_HIP(pgx::launch_reset_begin(env_mask, e->todo, e->regen, e->epoch, c.batch, s));
+    PGX_HIP(pgx::launch_reset_pool(p, s));
+    if (obs) {
+        pgx::StepParams sp = observe_params(e, obs);
+        sp.only = e->regen;
+        PGX_HIP(pgx::launch_step(sp, e->geo, s));
+    }
+    return PGX_OK;
+}
+
+int pgx_get_map_index(pgx_env* e, int32_t* out, void* stream) {
+    if (!e || !out) return fail_msg(PGX_E_INVALID, "pgx_get_map_index: null argument");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_get_map_index", false)) return rc;
+    const size_t bytes = (size_t)e->cfg.batch * sizeof(int32_t);
+    if (e->map_index) PGX_HIP(hipMemcpyAsync(out, e->map_index, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    else PGX_HIP(hipMemsetAsync(out, 0xFF, bytes, (hipStream_t)stream));
+    return PGX_OK;
+}
+
 // ---- snapshot / restore of the complete engine state (checkpoint-resume, `step_back`) ---------------------
 extern "C++" {
 namespace {
@@ -608,7 +753,8 @@ struct Segment {
     void* ptr;
     size_t bytes;
 };
-std::vector<Segment> snapshot_segments(pgx_env* e) {
+// with_pool: the layout of a handle with a map pool installed (map_index appended as the last segment)
+std::vector<Segment> snapshot_segments(pgx_env* e, bool with_pool) {
     const pgx_config& c = e->cfg;
     const size_t B = (size_t)c.batch, BA = B * c.num_agents, cells = (size_t)c.height * c.width;
     std::vector<Segment> seg = {
@@ -623,6 +769,7 @@ std::vector<Segment> snapshot_segments(pgx_env* e) {
         seg.push_back({e->comp_len, B * cells * 4});
         seg.push_back({e->comp_cells, B * cells * 4});
     }
+    if (with_pool) seg.push_back({e->map_index, B * 4});
     return seg;
 }
 size_t aligned16(size_t n) { return (n + 15) & ~(size_t)15; }
@@ -632,12 +779,20 @@ constexpr size_t SNAP_HEADER_BYTES = 64;
 struct SnapHeader {
     int32_t magic, abi, batch, num_agents, height, width, obs_radius, on_target, collision_system, max_episode_steps;
     int64_t total_bytes;
-    int32_t pad[4];
+    int32_t has_pool;  // 1: the last segment is map_index (a handle with a map pool); 0 otherwise
+    int32_t pad[3];
 };
 static_assert(sizeof(SnapHeader) == SNAP_HEADER_BYTES, "snapshot header layout");
-SnapHeader snapshot_header(pgx_env* e, int64_t total) {
+size_t snapshot_total(pgx_env* e, bool with_pool) {
+    size_t total = SNAP_HEADER_BYTES;
+    for (const Segment& s : snapshot_segments(e, with_pool)) total += aligned16(s.bytes);
+    return total;
+}
+SnapHeader snapshot_header(pgx_env* e, bool with_pool) {
     const pgx_config& c = e->cfg;
+    const int64_t total = (int64_t)snapshot_total(e, with_pool);
     SnapHeader h{};
+    h.has_pool = with_pool ? 1 : 0;
     h.magic = SNAP_MAGIC; h.abi = PGX_ABI_VERSION; h.batch = c.batch; h.num_agents = c.num_agents;
     h.height = c.height; h.width = c.width; h.obs_radius = c.obs_radius; h.on_target = c.on_target;
     h.collision_system = c.collision_system; h.max_episode_steps = c.max_episode_steps; h.total_bytes = total;
@@ -648,9 +803,7 @@ SnapHeader snapshot_header(pgx_env* e, int64_t total) {
 
 int64_t pgx_snapshot_bytes(pgx_env* e) {
     if (!e) return 0;
-    size_t total = SNAP_HEADER_BYTES;
-    for (const Segment& s : snapshot_segments(e)) total += aligned16(s.bytes);
-    return (int64_t)total;
+    return (int64_t)snapshot_total(e, e->pool_size > 0);
 }
 
 int pgx_save_snapshot(pgx_env* e, void* blob, void* stream) {
@@ -658,11 +811,12 @@ int pgx_save_snapshot(pgx_env* e, void* blob, void* stream) {
     DeviceGuard guard;
     if (const int rc = enter(guard, e, "pgx_save_snapshot", true)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const SnapHeader header = snapshot_header(e, pgx_snapshot_bytes(e));
+    const bool with_pool = e->pool_size > 0;
+    const SnapHeader header = snapshot_header(e, with_pool);
     PGX_HIP(hipMemcpyAsync(blob, &header, sizeof header, hipMemcpyHostToDevice, s));
     PGX_HIP(hipStreamSynchronize(s));  // `header` lives on this stack frame
     size_t off = SNAP_HEADER_BYTES;
-    for (const Segment& g : snapshot_segments(e)) {
+    for (const Segment& g : snapshot_segments(e, with_pool)) {
         PGX_HIP(hipMemcpyAsync((char*)blob + off, g.ptr, g.bytes, hipMemcpyDeviceToDevice, s));
         off += aligned16(g.bytes);
     }
@@ -677,7 +831,12 @@ int pgx_load_snapshot(pgx_env* e, const void* blob, void* stream) {
     SnapHeader got{};
     PGX_HIP(hipMemcpyAsync(&got, blob, sizeof got, hipMemcpyDeviceToHost, s));
     PGX_HIP(hipStreamSynchronize(s));
-    const SnapHeader want = snapshot_header(e, pgx_snapshot_bytes(e));
+    // a handle with a pool also takes a snapshot made without one (its envs then run no pool map: map_index = -1)
+    const bool with_pool = e->pool_size > 0 && got.has_pool != 0;
+    const SnapHeader want = snapshot_header(e, with_pool);
+    if (got.has_pool && !e->pool_size)
+        return fail_msg(PGX_E_INVALID, "snapshot was taken with a map pool installed; install a pool of the same size "
+                                       "(pgx_set_map_pool) before loading it");
     if (memcmp(&got, &want, sizeof want) != 0)
         return fail_msg(PGX_E_INVALID,
                         "snapshot does not belong to this configuration: blob has magic %08x abi %d batch %d agents %d map %dx%d "
@@ -688,10 +847,11 @@ int pgx_load_snapshot(pgx_env* e, const void* blob, void* stream) {
                         want.batch, want.num_agents, want.height, want.width, want.obs_radius, want.on_target,
                         want.collision_system, want.max_episode_steps, (long long)want.total_bytes);
     size_t off = SNAP_HEADER_BYTES;
-    for (const Segment& g : snapshot_segments(e)) {
+    for (const Segment& g : snapshot_segments(e, with_pool)) {
         PGX_HIP(hipMemcpyAsync(g.ptr, (const char*)blob + off, g.bytes, hipMemcpyDeviceToDevice, s));
         off += aligned16(g.bytes);
     }
+    if (e->map_index && !with_pool) PGX_HIP(hipMemsetAsync(e->map_index, 0xFF, (size_t)e->cfg.batch * sizeof(int32_t), s));
     e->has_state = true;
     return PGX_OK;
 }

@@ -51,6 +51,7 @@ enum : uint32_t { ACTIVE_BIT = 1u, ACTIVE_GHOST = 2u };
 // ---- instance generator "GEN v2" constants shared by the host generator and the device kernels ----
 constexpr uint64_t GEN_TAG_OBST = 0x4F42535400000000ull;   // 'OBST'
 constexpr uint64_t GEN_TAG_PLACE = 0x504C414300000000ull;  // 'PLAC'
+constexpr uint64_t GEN_TAG_POOL = 0x504F4F4C00000000ull;   // 'POOL': the map of a pool an env runs (docs/SPEC.md S10)
 inline uint32_t gen_density_threshold(float density) {      // obstacle <=> 24 hash bits < thr
     double t = (double)density * 16777216.0 + 0.5;
     if (t < 0.0) t = 0.0;
@@ -232,10 +233,26 @@ struct ResetParams {
     uint32_t *comp_begin, *comp_len, *comp_cells;  // lifelong only
     uint32_t* fail_count;       // envs that could not be filled
     OutsideParams outside;      // `empty_outside=False`
+    // map pool (launch_reset_pool only; scratch_map and labels unused there)
+    int32_t pool_size;            // M
+    const uint8_t* pool_maps;     // [M][H*W] 0/1
+    const uint32_t* pool_labels;  // [M][H*W] min-index component labels of the pool maps
+    int32_t* map_index;           // [B] pool index of the map each env runs
 };
 hipError_t launch_reset_begin(const uint8_t* mask, uint8_t* todo, uint8_t* regen, uint32_t* epoch, int batch,
                               hipStream_t s);
 hipError_t launch_reset_env(const ResetParams& p, hipStream_t s);
+// map pool: env e of the launch runs pool map k = ((sm64(instance_hash(seed, base + e, epoch, 0) ^ 'POOL') >> 32) * M) >> 32
+__host__ __device__ inline uint32_t gen_pool_pick(uint64_t h0, uint32_t num_maps) {
+    return (uint32_t)(((gen_sm64(h0 ^ GEN_TAG_POOL) >> 32) * (uint64_t)num_maps) >> 32);
+}
+hipError_t launch_reset_pool(const ResetParams& p, hipStream_t s);
+// normalises `count` maps of src into dst (0/1), labels their components and reduces each map's pair capacity
+// (sum over components of floor(size / 2)) into cap; cnt = one scratch slot of H*W words per map of the launch
+hipError_t launch_pool_label(const uint8_t* src, uint8_t* dst, uint32_t* labels, uint32_t* cnt, uint32_t* cap, int count,
+                             int H, int Wd, hipStream_t s);
+// map_index[b] = -1 for every env b a non-pool reset just rebuilt (regen[b] set, todo[b] cleared)
+hipError_t launch_clear_map_index(const uint8_t* regen, const uint8_t* todo, int32_t* map_index, int batch, hipStream_t s);
 hipError_t launch_pack_agents(const int32_t* agent_xy, const int32_t* target_xy, uint32_t* pos, uint32_t* tgt,
                               uint32_t* pos0, uint32_t* tgt0, uint8_t* active, uint32_t* tcount, size_t n,
                               int r, hipStream_t stream, NpGen* np_state = nullptr, const NpGen* np_state0 = nullptr);

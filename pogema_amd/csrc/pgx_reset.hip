@@ -323,6 +323,35 @@ __device__ void pack_phase(const uint8_t* __restrict__ obst, uint32_t* __restric
     }
 }
 
+// Installs a placed instance in env `env`: map bytes, agents, targets, step counter, metric accumulators, padded bitmap.
+__device__ __forceinline__ void commit_phase(const ResetParams& p, int env, const uint8_t* __restrict__ obst,
+                                             const uint32_t* pairs) {
+    const int tid = threadIdx.x;
+    const int cells = p.H * p.Wd;
+    uint8_t* env_map = p.map_u8 + (size_t)env * cells;
+    for (int c = tid; c < cells; c += 256) env_map[c] = obst[c];
+    const uint32_t pad = ((uint32_t)p.r << 16) | (uint32_t)p.r;
+    for (int i = tid; i < p.A; i += 256) {
+        const uint32_t s = pairs[2 * i], t = pairs[2 * i + 1];
+        const size_t gi = (size_t)env * p.A + i;
+        const uint32_t pc = (((s / p.Wd) << 16) | (s % p.Wd)) + pad;
+        const uint32_t tc = (((t / p.Wd) << 16) | (t % p.Wd)) + pad;
+        p.pos[gi] = pc;
+        p.pos0[gi] = pc;
+        p.tgt[gi] = tc;
+        p.tgt0[gi] = tc;
+        p.active[gi] = 1;
+        if (p.tcount) p.tcount[gi] = 0u;
+        if (p.np_state) p.np_state[gi] = p.np_state0[gi];
+    }
+    if (tid == 0) {
+        p.todo[env] = 0;
+        p.elapsed[env] = 0;
+        p.macc[env] = make_int4(0, 0, 0, 0);
+    }
+    pack_phase(obst, p.obst_bm + (size_t)env * p.bmw, p.H, p.Wd, p.r, p.wpr, p.bmw, p.outside, env);
+}
+
 }  // namespace
 
 // todo/regen flags and generation counters for one reset call
@@ -358,8 +387,7 @@ __global__ __launch_bounds__(256) void reset_env_kernel(const ResetParams p) {
     uint32_t* pairs = s_dyn + (LDS ? cells : 0);            // [2 * A]
     uint32_t* lab = p.labels + (size_t)local * cells;
     uint32_t* pend = p.pending + (size_t)local * cells;
-    uint8_t* env_map = p.map_u8 + (size_t)env * cells;
-    const uint8_t* obst = env_map;
+    const uint8_t* obst = p.map_u8 + (size_t)env * cells;
     if (!p.given_state) {
         uint8_t* draft = p.scratch_map + (size_t)local * cells;
         obst = draft;
@@ -388,34 +416,94 @@ __global__ __launch_bounds__(256) void reset_env_kernel(const ResetParams p) {
             if (tid == 0) atomicAdd(p.fail_count, 1u);
             return;
         }
-        // ---- commit -------------------------------------------------------------------------------
-        for (int c = tid; c < cells; c += 256) env_map[c] = draft[c];
-        const uint32_t pad = ((uint32_t)p.r << 16) | (uint32_t)p.r;
-        for (int i = tid; i < p.A; i += 256) {
-            const uint32_t s = pairs[2 * i], t = pairs[2 * i + 1];
-            const size_t gi = (size_t)env * p.A + i;
-            const uint32_t pc = (((s / p.Wd) << 16) | (s % p.Wd)) + pad;
-            const uint32_t tc = (((t / p.Wd) << 16) | (t % p.Wd)) + pad;
-            p.pos[gi] = pc;
-            p.pos0[gi] = pc;
-            p.tgt[gi] = tc;
-            p.tgt0[gi] = tc;
-            p.active[gi] = 1;
-            if (p.tcount) p.tcount[gi] = 0u;
-            if (p.np_state) p.np_state[gi] = p.np_state0[gi];
-        }
-        if (tid == 0) {
-            p.todo[env] = 0;
-            p.elapsed[env] = 0;
-            p.macc[env] = make_int4(0, 0, 0, 0);
-        }
-        pack_phase(draft, p.obst_bm + (size_t)env * p.bmw, p.H, p.Wd, p.r, p.wpr, p.bmw, p.outside, env);
+        commit_phase(p, env, draft, pairs);
     } else {
         ccl_phase<LDS>(obst, lab, forest, p.H, p.Wd);
     }
     if (p.lifelong)
         tables_phase(obst, lab, pend, p.comp_begin + (size_t)env * cells, p.comp_len + (size_t)env * cells,
                      p.comp_cells + (size_t)env * cells, p.Wd, cells, s_flag + 2);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Map pool (docs/SPEC.md S10).  pool_label_kernel runs once per installed pool: one workgroup per pool map normalises
+// it to 0/1, labels its components (ccl_phase, the same min-index labels) and reduces its pair capacity.
+// reset_pool_kernel is reset_env_kernel's sibling for pools: the env's map is pool[k], k drawn from attempt 0's key,
+// and its labels are the pool's -- no draft map, no per-env labelling, only the `pending` scratch slot per env.
+// ------------------------------------------------------------------------------------------------
+template <bool LDS>
+__global__ __launch_bounds__(256) void pool_label_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                         uint32_t* __restrict__ labels, uint32_t* __restrict__ cnt,
+                                                         uint32_t* __restrict__ cap, int H, int Wd) {
+    extern __shared__ uint32_t s_dyn[];  // [cells] forest when LDS
+    __shared__ uint32_t s_cap;
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const int cells = H * Wd;
+    const uint8_t* in = src + (size_t)m * cells;
+    uint8_t* map = dst + (size_t)m * cells;
+    uint32_t* lab = labels + (size_t)m * cells;
+    uint32_t* n = cnt + (size_t)m * cells;
+    for (int c = tid; c < cells; c += 256) {
+        map[c] = in[c] != 0 ? 1 : 0;
+        st<false>(n + c, 0u);
+    }
+    if (tid == 0) s_cap = 0u;
+    __syncthreads();
+    ccl_phase<LDS>(map, lab, s_dyn, H, Wd);
+    for (int c = tid; c < cells; c += 256)
+        if (!map[c]) atomicAdd(n + lab[c], 1u);
+    __syncthreads();
+    uint32_t pairs = 0u;
+    for (int c = tid; c < cells; c += 256)
+        if (!map[c] && lab[c] == (uint32_t)c) pairs += ld<false>(n + c) >> 1;
+    atomicAdd(&s_cap, pairs);
+    __syncthreads();
+    if (tid == 0) cap[m] = s_cap;
+}
+
+__global__ __launch_bounds__(256) void reset_pool_kernel(const ResetParams p) {
+    extern __shared__ uint32_t s_dyn[];  // pairs [2 * A]
+    __shared__ uint32_t s_flag[4];
+    const int local = blockIdx.x;
+    const int env = p.env_begin + local;
+    if (!p.todo[env]) return;
+    const int tid = threadIdx.x;
+    const int cells = p.H * p.Wd;
+    uint32_t* pairs = s_dyn;
+    uint32_t* pend = p.pending + (size_t)local * cells;
+    const uint32_t epoch = p.epoch[env];
+    const uint64_t env_global = (uint64_t)(p.env_index_base + env);
+    const uint32_t k = gen_pool_pick(gen_instance_hash(p.gen_seed, env_global, epoch, 0u), (uint32_t)p.pool_size);
+    const uint8_t* obst = p.pool_maps + (size_t)k * cells;
+    const uint32_t* lab = p.pool_labels + (size_t)k * cells;
+    bool ok = false;
+    for (int attempt = 0; attempt < p.max_retries && !ok; ++attempt) {
+        const uint64_t h = gen_instance_hash(p.gen_seed, env_global, epoch, (uint32_t)attempt);
+        for (int c = tid; c < cells; c += 256) st<false>(pend + c, 0u);
+        __syncthreads();
+        if (tid < 64) {
+            const int placed = place_phase(obst, lab, pend, pairs, p.A, cells, h);
+            if (tid == 0) s_flag[0] = placed == p.A ? 1u : 0u;
+        }
+        __syncthreads();
+        ok = s_flag[0] != 0u;
+        __syncthreads();
+    }
+    if (!ok) {
+        if (tid == 0) atomicAdd(p.fail_count, 1u);
+        return;
+    }
+    commit_phase(p, env, obst, pairs);
+    if (tid == 0) p.map_index[env] = (int32_t)k;
+    if (p.lifelong)
+        tables_phase(obst, lab, pend, p.comp_begin + (size_t)env * cells, p.comp_len + (size_t)env * cells,
+                     p.comp_cells + (size_t)env * cells, p.Wd, cells, s_flag + 2);
+}
+
+__global__ void clear_map_index_kernel(const uint8_t* __restrict__ regen, const uint8_t* __restrict__ todo,
+                                       int32_t* __restrict__ map_index, int batch) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < batch && regen[b] && !todo[b]) map_index[b] = -1;
 }
 
 // ---- launchers --------------------------------------------------------------------------------------
@@ -447,6 +535,28 @@ hipError_t launch_reset_env(const ResetParams& p, hipStream_t s) {
     } else {
         hipLaunchKernelGGL(reset_env_kernel<false>, dim3(p.env_count), dim3(256), dyn, s, p);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_reset_pool(const ResetParams& p, hipStream_t s) {
+    hipLaunchKernelGGL(reset_pool_kernel, dim3(p.env_count), dim3(256), (size_t)p.A * 8, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_pool_label(const uint8_t* src, uint8_t* dst, uint32_t* labels, uint32_t* cnt, uint32_t* cap, int count,
+                             int H, int Wd, hipStream_t s) {
+    const size_t forest = (size_t)H * Wd * 4;
+    if (forest <= 64 * 1024) {
+        if (hipError_t e = raise_lds_limit(reinterpret_cast<const void*>(&pool_label_kernel<true>), forest)) return e;
+        hipLaunchKernelGGL(pool_label_kernel<true>, dim3(count), dim3(256), forest, s, src, dst, labels, cnt, cap, H, Wd);
+    } else {
+        hipLaunchKernelGGL(pool_label_kernel<false>, dim3(count), dim3(256), 0, s, src, dst, labels, cnt, cap, H, Wd);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_clear_map_index(const uint8_t* regen, const uint8_t* todo, int32_t* map_index, int batch, hipStream_t s) {
+    hipLaunchKernelGGL(clear_map_index_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, regen, todo, map_index, batch);
     return hipGetLastError();
 }
 

@@ -32,6 +32,15 @@ def _instance_hash(seed: int, env: int, epoch: int = 0, attempt: int = 0) -> np.
     return _sm64(h ^ np.uint64(((epoch & 0xFFFFFFFF) << 32) | (attempt & 0xFFFFFFFF)))[0]
 
 
+TAG_POOL = 0x504F4F4C00000000  # 'POOL'
+
+
+def pool_pick(seed: int, env: int, epoch: int, num_maps: int) -> int:
+    """The map pool index global env `env` runs in generation `epoch` (docs/SPEC.md S10; pgx_reset.hip: gen_pool_pick)."""
+    r = int(_sm64(np.array([_instance_hash(seed, env, epoch, 0) ^ np.uint64(TAG_POOL)], np.uint64))[0])
+    return ((r >> 32) * int(num_maps)) >> 32
+
+
 def _first_distinct(h: np.uint64, tag: int, n: int, count: int) -> np.ndarray:
     """Indices into a list of length n: the first `count` distinct values of the candidate stream."""
     budget = 32 * n + 64

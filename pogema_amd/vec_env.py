@@ -29,6 +29,43 @@ def _as_device_index(device) -> int:
     return dev.index if dev.index is not None else torch.cuda.current_device()
 
 
+def parse_map_pool(maps) -> torch.Tensor:
+    """A map pool as uint8 [M, H, W] (1 = obstacle), on the device it came from (lists / text / numpy: the host).
+    Accepts a uint8 or bool tensor or array [M, H, W], or a list of GridConfig-style maps of one shape: lists of rows
+    (nonzero = obstacle) or text of '.' and '#' only.  Everything else is a ValueError naming what is wrong."""
+    if isinstance(maps, (torch.Tensor, np.ndarray)):
+        t = maps.detach() if isinstance(maps, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(maps))
+        if t.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"map_pool: a tensor or array pool must be uint8 or bool, got {t.dtype}")
+        if t.dim() != 3 or min(t.shape) < 1:
+            raise ValueError(f"map_pool: a tensor or array pool must have shape [M, H, W] with M, H, W >= 1, got "
+                             f"{tuple(t.shape)}")
+        return (t != 0).to(torch.uint8).contiguous()
+    if isinstance(maps, (str, bytes)) or not hasattr(maps, "__len__") or len(maps) == 0:
+        raise ValueError("map_pool: expected a uint8/bool tensor or array [M, H, W] or a non-empty list of maps")
+    out = []
+    for i, m in enumerate(maps):
+        if isinstance(m, str):
+            rows = [line for line in m.split()]
+            bad = sorted({ch for line in rows for ch in line} - set(".#"))
+            if bad:
+                raise ValueError(f"map_pool: map {i} has symbols {''.join(bad)!r}; pool maps are obstacles only ('.' free, "
+                                 f"'#' obstacle) -- agents and targets are drawn per env")
+            grid = [[1 if ch == "#" else 0 for ch in line] for line in rows]
+        else:
+            grid = [list(row) for row in (m.tolist() if hasattr(m, "tolist") else m)]
+        if not grid or not grid[0] or any(len(row) != len(grid[0]) for row in grid):
+            raise ValueError(f"map_pool: map {i} is not a non-empty rectangular list of rows")
+        arr = np.asarray(grid)
+        if arr.dtype.kind not in "biu":
+            raise ValueError(f"map_pool: map {i} holds non-integer cells ({arr.dtype})")
+        if out and arr.shape != out[0].shape:
+            raise ValueError(f"map_pool: map {i} is {arr.shape[0]}x{arr.shape[1]}, map 0 is "
+                             f"{out[0].shape[0]}x{out[0].shape[1]}: every map of a pool has one shape")
+        out.append((arr != 0).astype(np.uint8))
+    return torch.from_numpy(np.ascontiguousarray(np.stack(out)))
+
+
 class VecPogema(PlacementMixin):
     """`batch` independent POGEMA environments on one MI355X.
 
@@ -72,6 +109,15 @@ class VecPogema(PlacementMixin):
     allocator and `placement["fallback"]` says why.  `close()` keeps one set of zone buffers mapped for the next
     environment of the same shape (buffers.ParkedBuffers, PGX_POOL_CACHE_MB); `close(release=True)` does not.
 
+    `map_pool`: maps of one shape H x W (a uint8 / bool tensor or array [M, H, W], or a list of GridConfig-style maps:
+    rows or text of '.' and '#') that reset(seed), reset_where() and auto_reset="regenerate" draw from ON THE DEVICE --
+    env i runs pool map `map_index[i]`, picked from (seed, global env index, generation), with its agents placed as on
+    a shared `map` (docs/SPEC.md S10).  The pool sets the engine's map shape (GridConfig.size and density are not used
+    for the map) and is refused together with GridConfig.map / agents_xy / possible_*_xy.  `set_map_pool()` installs or
+    replaces one later (same shape; current instances are kept until an env's next reset); a map that cannot hold
+    num_agents start/target pairs is refused there with its index.  `map_index` (int32 [batch]) says which pool map each
+    env runs, -1 after any other install.  Device memory: 5 bytes per cell and pool map.
+
     `semantics`: switches for the three low-confidence recollections of the reference (pogema_amd/semantics.py).
     Seeds: `reset(seed)` selects the instances (maps, starts, targets); the lifelong target stream and the
     `empty_outside=False` obstacles are keyed by `GridConfig.seed` (fixed at construction) and the global env index.
@@ -80,9 +126,16 @@ class VecPogema(PlacementMixin):
     def __init__(self, grid_config: Optional[GridConfig] = None, batch: int = 1, device="cuda:0",
                  env_index_base: int = 0, auto_reset: Optional[bool] = None, reuse_buffers="recycle",
                  obs_dtype=torch.float32, semantics: Optional[Semantics] = None,
-                 placement_probe: Optional[bool] = None, placement_budget_gib=None):
+                 placement_probe: Optional[bool] = None, placement_budget_gib=None, map_pool=None):
         self.grid_config = grid_config if grid_config is not None else GridConfig(num_agents=2)
         gc = self.grid_config
+        pool = None
+        if map_pool is not None:  # checked before anything touches a device
+            self._check_pool_config(gc)
+            pool = parse_map_pool(map_pool)
+            if (semantics if semantics is not None else Semantics.from_env()).generator_rng == "numpy":
+                raise NotImplementedError("map_pool draws from the build's generator (docs/SPEC.md S10); "
+                                          "generator_rng='numpy' has no pool form")
         self.observation_type = gc.observation_type  # 'default' tensor, or 'POMAPF' / 'MAPF' dict views
         self._possible = gc.possible_agents_xy is not None or gc.possible_targets_xy is not None
         if self._possible and (gc.possible_agents_xy is None or gc.possible_targets_xy is None or gc.map is None):
@@ -95,8 +148,9 @@ class VecPogema(PlacementMixin):
         if not 1 <= int(gc.num_agents) <= _lib.MAX_AGENTS:
             raise ValueError(f"num_agents={gc.num_agents}: this engine supports 1..{_lib.MAX_AGENTS} (one lane per agent, one "
                              f"workgroup of at most 1024 lanes per environment) -- see README.md, Limits")
-        if max(gc.map_shape) > _lib.MAX_SIDE:
-            raise ValueError(f"map {gc.map_shape[0]}x{gc.map_shape[1]}: this engine supports sides up to {_lib.MAX_SIDE} -- see README.md, Limits")
+        map_shape = tuple(pool.shape[1:]) if pool is not None else gc.map_shape
+        if max(map_shape) > _lib.MAX_SIDE:
+            raise ValueError(f"map {map_shape[0]}x{map_shape[1]}: this engine supports sides up to {_lib.MAX_SIDE} -- see README.md, Limits")
         if not torch.cuda.is_available():
             raise RuntimeError("pogema_amd needs a HIP device (torch.cuda.is_available() is False); "
                                "there is no CPU fallback")
@@ -105,7 +159,7 @@ class VecPogema(PlacementMixin):
         self.num_agents = int(gc.num_agents)
         self.obs_radius = int(gc.obs_radius)
         self.window = 2 * self.obs_radius + 1
-        self.height, self.width = gc.map_shape
+        self.height, self.width = map_shape
         self.device_index = _as_device_index(device)
         self.device = torch.device("cuda", self.device_index)
         self.env_index_base = int(env_index_base)
@@ -179,10 +233,13 @@ class VecPogema(PlacementMixin):
         self._shared = None
         self._reset_seed = None
         self._initial = None
+        self._pool = None
         # episode metrics (fused metric wrappers): rows are refreshed on the step that ends an env's episode
         self.metrics = torch.zeros((self.batch, len(_lib.METRIC_NAMES)), dtype=torch.float32, device=self.device)
         self.episode_done = torch.zeros((self.batch,), dtype=torch.bool, device=self.device)
         _lib.check(self._lib.pgx_set_metrics_buffers(self._handle, self.metrics.data_ptr(), self.episode_done.data_ptr()))
+        if pool is not None:
+            self.set_map_pool(pool)
 
     # ------------------------------------------------------------------------------------------
     def close(self, release: bool = False):
@@ -233,12 +290,74 @@ class VecPogema(PlacementMixin):
         return int(self._lib.pgx_regenerate_failures(self._handle, self._stream()))
 
     # ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_pool_config(gc):
+        if gc.map is not None or gc.agents_xy is not None or gc.possible_agents_xy is not None \
+                or gc.possible_targets_xy is not None:
+            raise ValueError("map_pool cannot be combined with GridConfig.map, agents_xy/targets_xy or possible_*_xy: the "
+                             "pool gives the maps and the agents are placed on them per env")
+
+    def set_map_pool(self, maps) -> None:
+        """Install (or replace) the map pool that reset(seed), reset_where() and auto_reset='regenerate' draw from (class
+        docstring, docs/SPEC.md S10).  `maps`: see parse_map_pool; the shape must be this engine's (height, width).
+        Current instances are kept until each env's next reset.  Checks every map's capacity on the host (one device
+        sync): a map that cannot hold num_agents start/target pairs is a ValueError naming it, and leaves no pool
+        installed.  A pool of the same size reuses the engine's buffers, so a HIP graph captured over step() with
+        auto_reset='regenerate' draws from the new pool when replayed; call this outside the capture."""
+        self._check_pool_config(self.grid_config)
+        if self.semantics.generator_rng == "numpy":
+            raise NotImplementedError("map_pool draws from the build's generator; generator_rng='numpy' has no pool form")
+        pool = parse_map_pool(maps)
+        if tuple(pool.shape[1:]) != (self.height, self.width):
+            raise ValueError(f"map_pool: maps are {pool.shape[1]}x{pool.shape[2]}, this engine's are "
+                             f"{self.height}x{self.width}")
+        pool = pool.to(self.device)
+        if self._pool is not None and pool.data_ptr() == self._pool.data_ptr():
+            pool = pool.clone()
+        M = int(pool.shape[0])
+        cap = (C.c_int32 * M)()
+        rc = self._lib.pgx_set_map_pool(self._handle, pool.data_ptr(), M, cap, self._stream())
+        if rc != 0:
+            msg = self._lib.pgx_last_error().decode()
+            self._pool = None
+            if rc == -5:
+                raise ValueError(f"map_pool refused: {msg}")
+            _lib.check(rc)
+        self._pool = pool
+        self.pool_capacity = np.frombuffer(cap, dtype=np.int32).copy()
+
+    @property
+    def map_pool(self) -> Optional[torch.Tensor]:
+        """The installed pool, uint8 [M, H, W] on the device (1 = obstacle), or None."""
+        return self._pool
+
+    @property
+    def map_index(self) -> torch.Tensor:
+        """int32 [batch] (a fresh device tensor): the pool index of the map each env runs, -1 for an env whose instance
+        came from anywhere else (reset_from_state, random or shared-map resets, a snapshot taken without a pool)."""
+        out = torch.empty((self.batch,), dtype=torch.int32, device=self.device)
+        _lib.check(self._lib.pgx_get_map_index(self._handle, out.data_ptr(), self._stream()))
+        return out
+
+    def _pool_pick(self, seed0: int) -> np.ndarray:
+        """Host restatement of the device's map choice (docs/SPEC.md S10) for generation 0."""
+        from .generator_host import pool_pick
+        return np.array([pool_pick(seed0, self.env_index_base + b, 0, int(self._pool.shape[0]))
+                         for b in range(self.batch)], dtype=np.int64)
+
     def generate(self, seed: Optional[int] = None):
         """Host-side instance generation (engine's C++ generator); returns numpy
         (obstacles u8 [B,H,W], agents_xy i32 [B,A,2], targets_xy i32 [B,A,2])."""
         gc = self.grid_config
         B, H, Wd, A = self.batch, self.height, self.width, self.num_agents
         seed0 = self._resolve_seed(seed)
+        if self._pool is not None:
+            obstacles = np.ascontiguousarray(self._pool.cpu().numpy()[self._pool_pick(seed0)])
+            agents = np.empty((B, A, 2), dtype=np.int32)
+            targets = np.empty((B, A, 2), dtype=np.int32)
+            _lib.check(self._lib.pgx_place_agents(B, H, Wd, A, seed0, self.env_index_base, 10, 0, obstacles.ctypes.data, 0,
+                                                  agents.ctypes.data, targets.ctypes.data))
+            return obstacles, agents, targets
         if self._numpy_generator():
             from .nprng import np_generate_host
             obstacles, agents, targets, status = np_generate_host(self._numpy_seeds(seed0), H, Wd, A, gc.density, gc.map)
@@ -371,9 +490,16 @@ class VecPogema(PlacementMixin):
     def reset(self, seed: Optional[int] = None, options=None):
         """gymnasium-style reset: draws fresh instances ON THE DEVICE (env i draws instance
         seed + env_index_base + i; `generate()` yields the same instances on the host) and returns (obs, infos).
+        With a map pool installed, env i runs the pool map chosen for it (`map_index`) with agents placed on it.
         With an explicit `map` AND `agents_xy`/`targets_xy` in the GridConfig nothing is random: that state is installed."""
         gc = self.grid_config
-        if self._numpy_generator():
+        if self._pool is not None:
+            resolved = self._resolve_seed(seed)
+            _lib.check(self._lib.pgx_reset_pool(self._handle, resolved, None, 10, self._stream()))
+            self._reset_seed = resolved
+            self._refresh_initial()
+            obs = self._wrap_obs(self.observe())
+        elif self._numpy_generator():
             from .nprng import np_generate
             resolved = self._resolve_seed(seed)
             with np.errstate(over="ignore"):
@@ -420,10 +546,13 @@ class VecPogema(PlacementMixin):
                                       "reset(seed=...) (upstream re-creates the same instance for a fixed seed)")
         if seed is None:
             seed = self._reset_seed
-        shared = self._shared_map_tensor()
-        _lib.check(self._lib.pgx_reset_random(self._handle, float(gc.density), self._resolve_seed(seed),
-                                              shared.data_ptr() if shared is not None else None, mask.data_ptr(), 10,
-                                              self._stream()))
+        if self._pool is not None:
+            _lib.check(self._lib.pgx_reset_pool(self._handle, self._resolve_seed(seed), mask.data_ptr(), 10, self._stream()))
+        else:
+            shared = self._shared_map_tensor()
+            _lib.check(self._lib.pgx_reset_random(self._handle, float(gc.density), self._resolve_seed(seed),
+                                                  shared.data_ptr() if shared is not None else None, mask.data_ptr(), 10,
+                                                  self._stream()))
         old = self._initial
         self._refresh_initial()  # only the flagged envs have a new initial state
         keep = mask == 0
@@ -570,12 +699,17 @@ class VecPogema(PlacementMixin):
         if self.regenerate:
             if self._reset_seed is None:
                 raise RuntimeError("auto_reset='regenerate' needs reset(seed) first (random instances)")
-            if self._shared is None and self.grid_config.map is not None:
-                self._shared = self._shared_map_tensor()
-            _lib.check(self._lib.pgx_regenerate(
-                self._handle, self.episode_done.data_ptr(), float(self.grid_config.density), self._reset_seed,
-                self._shared.data_ptr() if self._shared is not None else None, 3,
-                obs.data_ptr() if compute_obs else None, self._stream()))
+            if self._pool is not None:
+                _lib.check(self._lib.pgx_regenerate_pool(
+                    self._handle, self.episode_done.data_ptr(), self._reset_seed, 3,
+                    obs.data_ptr() if compute_obs else None, self._stream()))
+            else:
+                if self._shared is None and self.grid_config.map is not None:
+                    self._shared = self._shared_map_tensor()
+                _lib.check(self._lib.pgx_regenerate(
+                    self._handle, self.episode_done.data_ptr(), float(self.grid_config.density), self._reset_seed,
+                    self._shared.data_ptr() if self._shared is not None else None, 3,
+                    obs.data_ptr() if compute_obs else None, self._stream()))
         if self.semantics.bad_action == "flag":  # the reference's IndexError on MOVES[action]; one host sync per step
             bad = int(self._lib.pgx_bad_action_count(self._handle, self._stream()))
             if bad < 0:
@@ -750,7 +884,10 @@ class VecPogema(PlacementMixin):
 
     def load_state(self, state) -> None:
         blob = state["engine"].to(self.device).contiguous()
-        if blob.numel() != int(self._lib.pgx_snapshot_bytes(self._handle)):
+        sizes = {int(self._lib.pgx_snapshot_bytes(self._handle))}
+        if self._pool is not None:  # a snapshot taken without a pool: no map_index segment (16-byte aligned)
+            sizes.add(min(sizes) - (4 * self.batch + 15) // 16 * 16)
+        if blob.numel() not in sizes:
             raise ValueError("snapshot size does not match this environment's configuration")
         # (the engine compares the blob's header -- geometry, modes, byte count -- with this handle's and refuses a mismatch)
         _lib.check(self._lib.pgx_load_snapshot(self._handle, blob.data_ptr(), self._stream()))
