@@ -355,6 +355,34 @@ int pgx_set_targets(pgx_env* env, const int32_t* target_xy, const uint8_t* agent
 #define PGX_EXPERT_AGENTS_AS_OBSTACLES 1
 int pgx_expert_actions(pgx_env* env, int32_t flags, void* actions, int32_t action_dtype, int32_t* distance, void* stream);
 
+/* Cost-to-go windows (docs/SPEC.md S11), read from the current device state -- the state the next pgx_step reads, which
+ * this call does not change.  For every agent, its (2r+1) x (2r+1) window (r = obs_radius) in the orientation of
+ * observation plane 0:
+ *   out   device i32 [batch, agents, 2r+1, 2r+1]; out[b, i, u, v] is the 4-connected shortest-path length from cell
+ *         (x - r + u, y - r + v) to the agent's current target over the free cells of the height x width map (as
+ *         pgx_expert_actions' distance: cells outside the map are never traversed); -1 outside the map, on an obstacle,
+ *         for a cell not connected to the target, for every cell when the target is an obstacle, and for every cell of
+ *         an agent that is not active (bit 0 of is_active clear).  The centre of an active agent equals
+ *         pgx_expert_actions' distance without PGX_EXPERT_AGENTS_AS_OBSTACLES.
+ *   flags reserved, must be 0.
+ * The handle caches one distance field per agent and rebuilds it only when the agent is active and its field is missing,
+ * was built for another target cell, or was built on another map of its env (a changed map invalidates the whole env);
+ * every other field is reused, however the state changed (resets, auto-reset, map pools, pgx_set_targets, lifelong
+ * draws, pgx_load_snapshot).  A call without a state change since the previous one builds nothing.
+ * The first call allocates the cache, pgx_cost_to_go_bytes() bytes that the handle keeps until pgx_destroy; made inside a
+ * graph capture, that first call returns PGX_E_STATE instead (make it once outside), and a failed allocation returns
+ * PGX_E_NOMEM / PGX_E_HIP naming the bytes.  Afterwards asynchronous on `stream`, no host sync, capturable in a HIP graph.
+ * PGX_E_STATE before the first reset, like pgx_step. */
+int pgx_cost_to_go(pgx_env* env, int32_t flags, int32_t* out, void* stream);
+/* Device bytes of pgx_cost_to_go's cache for `cfg`, needing no device: 16 (build counter) + the fields, B * A * H * W
+ * cells of 2 bytes when H * W <= 65536 (a distance is at most 65534, 0xFFFF is "unreachable") and of 4 bytes above,
+ * rounded up to a multiple of 16 + 4 * B * A (target tags) + 4 * B * H * ceil(W / 32) (map copies).  Returns the status
+ * code of pgx_check_config for a configuration it refuses. */
+int64_t pgx_cost_to_go_bytes(const pgx_config* cfg);
+/* Distance fields pgx_cost_to_go has built since the handle was created (0 before its first call).  Synchronises
+ * `stream`. */
+int64_t pgx_cost_to_go_builds(pgx_env* env, void* stream);
+
 /* Number of out-of-range actions (outside 0..4) that ACTIVE agents submitted since the last call (bad_action =
  * PGX_BAD_ACTION_FLAG only; otherwise always 0).  Inactive agents' actions are never looked at, as in the reference's
  * `if self.grid.is_active[agent_idx]` guards.  Synchronises `stream`, then clears the counter.  The host side turns a

@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = (
     "pgx_buffers_create", "pgx_buffers_ptr", "pgx_buffers_get_info", "pgx_buffers_destroy", "pgx_set_targets",
     "pgx_np_streams", "pgx_np_streams_host", "pgx_np_generate", "pgx_np_generate_host", "pgx_rollout", "pgx_buffers_stride", "pgx_buffers_drop", "pgx_xcd_shares", "pgx_xcd_tune", "pgx_buffers_create_at", "pgx_time_observe_pair", "pgx_buffers_va_reserved", "pgx_get_geometry",
     "pgx_expert_actions", "pgx_set_map_pool", "pgx_reset_pool", "pgx_regenerate_pool", "pgx_get_map_index",
+    "pgx_cost_to_go", "pgx_cost_to_go_bytes", "pgx_cost_to_go_builds",
 )
 
 
@@ -172,6 +173,12 @@ def load() -> C.CDLL:
     lib.pgx_rollout.restype = C.c_int
     lib.pgx_expert_actions.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.pgx_expert_actions.restype = C.c_int
+    lib.pgx_cost_to_go.argtypes = [vp, i32, vp, vp]
+    lib.pgx_cost_to_go.restype = C.c_int
+    lib.pgx_cost_to_go_bytes.argtypes = [C.POINTER(PgxConfig)]
+    lib.pgx_cost_to_go_bytes.restype = i64
+    lib.pgx_cost_to_go_builds.argtypes = [vp, vp]
+    lib.pgx_cost_to_go_builds.restype = i64
     lib.pgx_set_map_pool.argtypes = [vp, vp, i32, vp, vp]
     lib.pgx_set_map_pool.restype = C.c_int
     lib.pgx_reset_pool.argtypes = [vp, u64, vp, i32, vp]

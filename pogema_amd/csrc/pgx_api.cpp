@@ -103,6 +103,8 @@ struct pgx_env {
     DevBuf<uint32_t> pool_labels;         // [M][H*W] min-index component labels
     DevBuf<uint32_t> pool_cap;            // [M] start/target pairs each map can hold
     DevBuf<int32_t> map_index;            // [B] pool index of each env's map, -1 after a non-pool install
+    // cost-to-go cache (docs/SPEC.md S11, pgx::cost_to_go_layout), allocated by the first pgx_cost_to_go
+    DevBuf<uint8_t> c2g;
 };
 
 namespace {
@@ -971,6 +973,79 @@ int pgx_expert_actions(pgx_env* e, int32_t flags, void* actions, int32_t action_
     p.distance = distance;
     PGX_HIP(pgx::launch_expert(p, (hipStream_t)stream));
     return PGX_OK;
+}
+
+// ---- cost-to-go windows (docs/SPEC.md S11) --------------------------------------------------------------
+int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
+    if (!cfg) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go_bytes: null argument");
+    pgx_env* e = nullptr;
+    const int rc = create_host_side(cfg, 0, &e);
+    delete e;
+    if (rc) return rc;
+    return (int64_t)pgx::cost_to_go_layout(cfg->batch, cfg->num_agents, cfg->height, cfg->width).bytes;
+}
+
+int pgx_cost_to_go(pgx_env* e, int32_t flags, int32_t* out, void* stream) {
+    if (!e || !out) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: null argument");
+    if (flags != 0) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: flags must be 0, got 0x%x", flags);
+    if (reinterpret_cast<uintptr_t>(out) & 3) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: out is not 4-byte aligned");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_cost_to_go", true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const pgx_config& c = e->cfg;
+    const pgx::CostToGoLayout l = pgx::cost_to_go_layout(c.batch, c.num_agents, c.height, c.width);
+    if (!e->c2g) {
+        // the cache: allocated on first use, so that callers who never ask for windows never pay for it
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        PGX_HIP(hipStreamIsCapturing(s, &cap));
+        if (cap != hipStreamCaptureStatusNone)
+            return fail_msg(PGX_E_STATE, "pgx_cost_to_go: the first call allocates %zu bytes for the distance-field cache; "
+                                     "make it once outside graph capture", l.bytes);
+        PGX_HIP(pgx::prepare_cost_to_go(c.height, c.width));
+        const hipError_t err = e->c2g.alloc(l.bytes);
+        if (err != hipSuccess) {
+            (void)hipGetLastError();  // the failed allocation must not surface as the next launch's error
+            return fail_msg(alloc_code(err), "pgx_cost_to_go: distance-field cache of %zu bytes: %s", l.bytes,
+                            hipGetErrorString(err));
+        }
+        // no field, counter 0, an all-obstacle map copy (any installed map differs or leaves every tag cleared)
+        const hipError_t e0 = hipMemsetAsync(e->c2g, 0, l.field_off, s);
+        const hipError_t e1 = e0 != hipSuccess ? e0 : hipMemsetAsync(e->c2g + l.tag_off, 0xFF, l.map_off - l.tag_off, s);
+        const hipError_t e2 = e1 != hipSuccess ? e1 : hipMemsetAsync(e->c2g + l.map_off, 0, l.bytes - l.map_off, s);
+        if (e2 != hipSuccess) {
+            e->c2g.reset();
+            return fail_msg(PGX_E_HIP, "pgx_cost_to_go: clearing the cache failed: %s", hipGetErrorString(e2));
+        }
+    }
+    pgx::CostToGoParams p{};
+    p.batch = c.batch;
+    p.A = c.num_agents;
+    p.H = c.height;
+    p.W = c.width;
+    p.r = c.obs_radius;
+    p.wpr = e->wpr;
+    p.bmw = e->bmw;
+    p.obst = e->obst;
+    p.pos = e->pos;
+    p.tgt = e->tgt;
+    p.active = e->active;
+    p.map_bits = reinterpret_cast<uint32_t*>(e->c2g + l.map_off);
+    p.tag = reinterpret_cast<uint32_t*>(e->c2g + l.tag_off);
+    p.field = e->c2g + l.field_off;
+    p.builds = reinterpret_cast<unsigned long long*>(e->c2g + l.builds_off);
+    p.out = out;
+    PGX_HIP(pgx::launch_cost_to_go(p, s));
+    return PGX_OK;
+}
+
+int64_t pgx_cost_to_go_builds(pgx_env* e, void* stream) {
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_cost_to_go_builds", false)) return rc;
+    if (!e->c2g) return 0;
+    unsigned long long n = 0;
+    PGX_HIP(hipMemcpyAsync(&n, e->c2g, sizeof n, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    PGX_HIP(hipStreamSynchronize((hipStream_t)stream));
+    return (int64_t)n;
 }
 
 int pgx_set_targets(pgx_env* e, const int32_t* target_xy, const uint8_t* agent_mask, void* stream) {

@@ -283,4 +283,26 @@ size_t expert_occupancy_words(int batch, int H, int W);
 hipError_t prepare_expert(int H, int W);
 hipError_t launch_expert(const ExpertParams& p, hipStream_t stream);
 
+// ---- cost-to-go windows (pgx_cost2go.hip) --------------------------------------------------------------
+// One device allocation per handle, made by the first pgx_cost_to_go: [16 B build counter][fields, padded to 16 B]
+// [target tags][map bits].
+struct CostToGoLayout {
+    size_t cell_bytes;                       // 2 when H * W <= 65536, else 4
+    size_t builds_off, field_off, tag_off, map_off, bytes;
+};
+CostToGoLayout cost_to_go_layout(int batch, int A, int H, int W);
+struct CostToGoParams {
+    int32_t batch, A, H, W, r, wpr, bmw;
+    const uint32_t* obst;    // [B][bmw] padded obstacle bitmaps
+    const uint32_t *pos, *tgt;
+    const uint8_t* active;
+    uint32_t* map_bits;      // [B][H][ceil(W/32)] free bits the env's fields were built on
+    uint32_t* tag;           // [B][A] packed padded target each field was built for; all ones: no field
+    void* field;             // [B][A][H*W] distance to the tag's cell, u16 or u32 (cell_bytes); all ones: unreachable
+    unsigned long long* builds;  // [1] fields built since the cache was allocated
+    int32_t* out;            // [B][A][2r+1][2r+1]
+};
+hipError_t prepare_cost_to_go(int H, int W);
+hipError_t launch_cost_to_go(const CostToGoParams& p, hipStream_t stream);
+
 }  // namespace pgx

@@ -179,6 +179,11 @@ class Pogema:
         actions, _ = self._vec.expert_actions(agents_as_obstacles=agents_as_obstacles)
         return [int(a) for a in actions[0].cpu().numpy()]
 
+    def cost_to_go(self):
+        """The cost-to-go window of every agent (VecPogema.cost_to_go) as a list of int32 (W, W) numpy arrays."""
+        w = self._vec.cost_to_go()[0].cpu().numpy()
+        return [w[i] for i in range(w.shape[0])]
+
     def _metrics_dict(self, values):
         from ._lib import METRIC_NAMES
         metrics = {k: float(x) for k, x in zip(METRIC_NAMES, values)}

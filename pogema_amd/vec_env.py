@@ -857,6 +857,34 @@ class VecPogema(PlacementMixin):
                                                 self._ACTION_CODE[actions.dtype], distance.data_ptr(), self._stream()))
         return actions, distance
 
+    def cost_to_go(self, out=None) -> torch.Tensor:
+        """Cost-to-go windows (docs/SPEC.md S11), computed on the device from the current state -- the state the next
+        step() reads, which this call leaves untouched.  Returns int32 [batch, agents, W, W] (W = 2 * obs_radius + 1, the
+        orientation of observation plane 0): the 4-connected BFS distance from each window cell to the agent's target
+        over the map's free cells; -1 outside the map, on obstacles, for unreachable cells and for every cell of an
+        inactive agent.  The centre equals expert_actions()' distance.  One distance field per agent is cached on the
+        device and rebuilt only when the agent's target cell or its env's map changed (cost_to_go_builds counts them).
+        The first call allocates that cache (pgx_cost_to_go_bytes) and must be made outside a graph capture; later calls
+        are stream-ordered, need no host sync and can be captured.  `out`: a caller-owned contiguous int32 tensor of
+        that shape on this device."""
+        shape = (self.batch, self.num_agents, self.window, self.window)
+        if out is not None:
+            if (out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous()
+                    or out.device != self.device):
+                raise ValueError(f"out must be a contiguous int32 tensor of shape {shape} on {self.device}")
+        else:
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        _lib.check(self._lib.pgx_cost_to_go(self._handle, 0, out.data_ptr(), self._stream()))
+        return out
+
+    @property
+    def cost_to_go_builds(self) -> int:
+        """Distance fields cost_to_go() has built since this env was created (synchronises the stream)."""
+        n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
+        if n < 0:
+            _lib.check(int(n))
+        return int(n)
+
     def _wrap_obs(self, obs: torch.Tensor):
         """'default': the float32 tensor.  'POMAPF' / 'MAPF' (upstream `PogemaBase._pomapf_obs` / `_mapf_obs`):
         dict views over the same planes plus coordinates relative to each agent's start cell (and, for MAPF,
