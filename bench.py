@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X-native POGEMA step engine.
 
-    python bench.py --gpus N --steps K --warmup W [--windows 5] [--workload cfg2] [--global-batch G]
+    python bench.py --gpus N --steps K --warmup W [--full] [--windows 5] [--workload cfg2] [--global-batch G]
 
 A "step" is one pass of the hot path (`VecPogema.step` -> pgx_step -> one HIP kernel launch) over one batch of
 synthetic input: BASELINE.json configs[2] by default -- 8192 envs per GPU, 64x64 maps, 64 agents, obs_radius 5,
 density 0.3, random-obstacle maps, uniform random actions already resident in HBM.
 Metric: agent-steps/sec, whole job = (envs over all ranks) * agents * K / max-over-ranks wall time of K steps.
+A plain run does only what that figure needs: it builds the engine, warms up, times the K steps, writes the outputs when
+`--dump-outputs` is given, and prints the line (everything in it comes from the timed engine itself).  `--full` adds what
+takes runs of its own: the CPU baselines (`cpu_baseline`), the window into buffers as torch's allocator places them
+(`roofline.default_placement_kernel_ms`) and the `secondary` figures -- held pairs, two pipelined engines, K-step rollout
+launches, HIP graphs, the host-side gather (also for N > 1) and the other BASELINE configs.  `--no-cpu-baseline`,
+`--no-default-placement` and `--no-extras` take single legs out of a `--full` run; they change nothing without it.
 
 Launch contract:
   * under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` every process is one rank
@@ -994,12 +1000,16 @@ def make_parser():
                     help="HBM the engine's zone walk may hold for its 1-3 s: default = the product default (walk only on a "
                          "device that is evidently ours, half of the free memory); half | all | a number of GiB = explicit")
     ap.add_argument("--graph", type=int, default=0, help="capture this many steps in one HIP graph and replay it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the CPU baselines, the window into "
+                         "torch-placed buffers and the secondary figures (held pairs, pipelined engines, rollout, HIP graph, "
+                         "host-side gather, the other BASELINE configs); off by default: a plain run prints the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-default-placement", action="store_true",
-                    help="skip the extra window that times the unprobed (default allocator) buffers")
+                    help="with --full: skip the extra window that times the unprobed (default allocator) buffers")
     ap.add_argument("--no-obs", action="store_true", help="diagnostic: skip the observation write")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary figures (two pipelined engines; K-step rollout launches)")
+                    help="with --full: skip the secondary figures (two pipelined engines; K-step rollout launches ...)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what their last step returned as DIR/<name>.npy (float32; at most "
@@ -1145,7 +1155,7 @@ def main(argv=None):
 
     # the same workload into buffers as torch's allocator hands them out (no zone placement), AFTER the main measurement:
     # allocating and freeing them first would leave holes that the zone walk of the main run falls into
-    if not args.stub and not args.no_default_placement and world == 1:
+    if args.full and not args.stub and not args.no_default_placement and world == 1:
         plain = EngineStep(args, rank, device, batch, env_base, size, agents, r, placement_probe=False)
         plain.run(max(args.warmup, 4))
         _, k = timed_windows(plain, 1)
@@ -1154,9 +1164,10 @@ def main(argv=None):
         del plain
         torch.cuda.empty_cache()
 
-    # secondary figures, never `value`: the same work without the launch boundary in the way
+    # secondary figures (--full only), never `value`: the same work without the launch boundary in the way
     extras = {}
-    if (not args.stub and not args.no_extras and world == 1 and args.graph <= 0 and args.auto_reset == "restore"
+    want_extras = args.full and not args.no_extras
+    if (not args.stub and want_extras and world == 1 and args.graph <= 0 and args.auto_reset == "restore"
             and not args.no_obs and args.buffers != 1):
         n = min(args.steps, 1000)
         extra_errors = {}
@@ -1235,9 +1246,9 @@ def main(argv=None):
                 torch.cuda.empty_cache()
         if extra_errors:
             extras["errors"] = extra_errors
-    elif args.stub and not args.no_extras and world == 1 and headline_form(args, batch, per_gpu):
+    elif args.stub and want_extras and world == 1 and headline_form(args, batch, per_gpu):
         extras["workloads"] = {name: stub_workload(name) for name in ("cfg1", "cfg3", "cfg4")}
-    elif not args.stub and not args.no_extras and world > 1 and args.graph <= 0 and not args.no_obs:
+    elif not args.stub and want_extras and world > 1 and args.graph <= 0 and not args.no_obs:
         # N > 1: the gather is the one cross-rank piece of the product path -- every rank takes part (shared segment).  A
         # failure on any rank must not cost the line: inside measure_host_gather every synchronisation point is an
         # all_reduce(MIN) of an ok flag over gloo, so all ranks leave the figure at the same call
@@ -1285,7 +1296,7 @@ def main(argv=None):
                            f"workload {args.workload}, obs {args.obs_dtype}{variant}",
             "value": value, "unit": "agent-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": scaling,
-            "vs_baseline": None, "dtype": "u32", "data": "stub" if args.stub else "synthetic",
+            "vs_baseline": None, "dtype": "u32", "data": "stub" if args.stub else "synthetic", "full": bool(args.full),
             "windows": {"n": args.windows, "statistic": "median", "steps_each": args.steps,
                         "ms_per_step": [w / args.steps * 1e3 for w in walls]},
             "config": {"workload": f"BASELINE.json configs[{args.workload[-1]}]: {total_envs} envs over {world} GPU(s) "
@@ -1324,9 +1335,9 @@ def main(argv=None):
                          "slowest_rank": max(range(len(per_rank)), key=lambda i: per_rank[i]["kernel_ms"]),
                          "zone_walks_in_process": None if args.stub else _walks_in_process(),
                          "algorithmic_bytes_per_agent_step": bpas, "algorithmic_bytes_per_launch": alg_bytes,
-                         "profile_command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-default-placement "
-                                            "--no-cpu-baseline --no-extras  (the default-placement window and the secondary "
-                                            "figures launch the same kernel on other buffers / half batches; profiles/r6/README.md)"},
+                         "profile_command": "rocprofv3 --kernel-trace --stats -- python3 bench.py  (without --full: its "
+                                            "default-placement window and secondary figures launch the same kernel on other "
+                                            "buffers / half batches; profiles/r6/README.md)"},
         }
         if "pipelined" in extras:
             e = extras["pipelined"]
@@ -1370,7 +1381,7 @@ def main(argv=None):
         if dumped is not None:
             line["dump_outputs"] = dumped
         line["box"] = fingerprint
-        if world == 1 and not args.no_cpu_baseline and not args.stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.stub:
             try:  # the baseline leg must never cost the measured line
                 line["cpu_baseline"] = cpu_baseline(size, agents, r, args.collision, args.density, args.max_episode_steps,
                                                     args.cpu_seconds)
@@ -1381,7 +1392,7 @@ def main(argv=None):
             except Exception as exc:  # noqa: BLE001
                 line["cpu_baseline"] = {"value": None, "unit": "agent-steps/s", "cores": 0, "kind": "port",
                                         "sample": f"FAILED: {exc!r}"}
-        elif world == 1 and not args.no_cpu_baseline and args.stub:  # (tests: the configs[0] leg runs on the CPU for real)
+        elif args.full and world == 1 and not args.no_cpu_baseline and args.stub:  # (tests: the configs[0] leg runs on the CPU for real)
             line["cpu_baseline"] = {"value": None, "unit": "agent-steps/s", "cores": 0, "kind": "port", "sample": "stub",
                                     "configs0_python_literal": configs0_cpu_baseline(0.3)}
         print(json.dumps(line), flush=True)

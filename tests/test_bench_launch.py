@@ -111,11 +111,12 @@ def test_rccl_fallback_is_a_collective_decision(fake):
 
 
 def test_default_form_carries_every_baseline_config():
-    """the driver's one line (N = 1, default workload) carries configs[1], the configs[3] shard and
+    """the driver's one `--full` line (N = 1, default workload) carries configs[1], the configs[3] shard and
     configs[4] under secondary.workloads with a fixed key set, and the configs[0] shape (size 8, 2 agents, r 3, ONE env) on
     the CPU under cpu_baseline.configs0_python_literal.  Stub mode pins the keys; the values are measured on the GPU box."""
     from bench import WORKLOAD_KEYS
-    line = _stub_line(_run(["--gpus", "1", "--stub", "--steps", "5", "--warmup", "1", "--windows", "1"]))
+    line = _stub_line(_run(["--gpus", "1", "--stub", "--steps", "5", "--warmup", "1", "--windows", "1", "--full"]))
+    assert line["full"] is True
     wl = line["secondary"]["workloads"]
     assert sorted(wl) == ["cfg1", "cfg3", "cfg4"]
     for name, rec in wl.items():
@@ -126,8 +127,27 @@ def test_default_form_carries_every_baseline_config():
     assert c0["value"] > 0 and c0["cores"] == 1 and "size=8, num_agents=2, obs_radius=3" in c0["sample"]
     assert c0["c_port"]["value"] > 0
     # a non-default workload does not drag the others along
-    other = _stub_line(_run(["--gpus", "1", "--stub", "--steps", "5", "--warmup", "1", "--windows", "1", "--workload", "cfg3"]))
+    other = _stub_line(_run(["--gpus", "1", "--stub", "--steps", "5", "--warmup", "1", "--windows", "1", "--workload", "cfg3",
+                             "--full"]))
     assert "workloads" not in (other.get("secondary") or {})
+
+
+def test_plain_run_measures_the_headline_only():
+    """Without `--full` the line is the headline and what the timed engine itself says: no CPU baseline, no secondary figure
+    and no default-placement window is measured; the headline keys read as they do under `--full`."""
+    plain = _stub_line(_run(["--gpus", "1", "--stub", "--steps", "5", "--warmup", "1"]))
+    assert plain["full"] is False
+    assert "secondary" not in plain and "cpu_baseline" not in plain
+    assert plain["roofline"]["default_placement_kernel_ms"] is None
+    full = _stub_line(_run(["--gpus", "1", "--stub", "--steps", "5", "--warmup", "1", "--full"]))
+    assert "secondary" in full and "cpu_baseline" in full
+    for key in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus", "scaling", "data"):
+        assert plain[key] == full[key], key
+    assert set(plain) | {"secondary", "cpu_baseline"} == set(full)
+    assert plain["value"] == pytest.approx(8192 * 64 * 5 / (plain["ms_per_step"] * 5 * 1e-3), rel=1e-6)
+    # the legs of a `--full` run can still be taken out one by one
+    lean = _stub_line(_run(["--gpus", "1", "--stub", "--steps", "5", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"]))
+    assert "secondary" not in lean and "cpu_baseline" not in lean
 
 
 def test_launcher_counts_devices_from_sysfs_not_hip(monkeypatch, tmp_path):

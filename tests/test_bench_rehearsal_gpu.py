@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 QUICK = ["--steps", "40", "--warmup", "5", "--windows", "2", "--no-cpu-baseline", "--no-extras", "--no-default-placement"]
-WITH_GATHER = [a for a in QUICK if a != "--no-extras"]  # N > 1: the only secondary figure is the host-side gather
+WITH_GATHER = [a for a in QUICK if a != "--no-extras"] + ["--full"]  # N > 1: the only secondary figure is the host-side gather
 
 
 def _check_per_rank(line, world):
@@ -137,7 +137,7 @@ def test_a_failed_walk_is_paid_once_by_the_whole_bench():
     """VERDICT r4 #1b at the level of bench.py: on a GPU where the walk finds nothing (forced here: PGX_ZONE_SCAN accepts no
     candidate) the headline engine walks ONCE; the secondary engines (two pipelined halves, the rollout ring) reuse the
     verdict instead of holding the memory three more times."""
-    args = ["--steps", "40", "--warmup", "5", "--windows", "2", "--no-cpu-baseline"]
+    args = ["--steps", "40", "--warmup", "5", "--windows", "2", "--full", "--no-cpu-baseline"]
     p = subprocess.run([sys.executable, BENCH] + args, capture_output=True, text=True, timeout=900,
                        env=_env(PGX_ZONE_SCAN="1", PGX_ZONE_SPACER_GIB="24"))
     line = _line(p)

@@ -2,10 +2,10 @@
 # benches of every BASELINE workload with the box fingerprint, the headline under both walk budgets, profiles
 O=gpurun_out/${1:-r4f}; mkdir -p $O
 bash tools/box_probe.sh $O/box.json > $O/box_probe.log 2>&1
-python bench.py > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-python bench.py --placement-budget all --no-cpu-baseline --no-extras > $O/bench_cfg2_budget_all.json 2> $O/bench_cfg2_budget_all.err
-python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_cfg2_driver_form.json 2> $O/bench_cfg2_driver_form.err
-for wl in cfg3 cfg1 cfg4; do python bench.py --workload $wl --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err; done
+python bench.py --full > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python bench.py --full --placement-budget all --no-cpu-baseline --no-extras > $O/bench_cfg2_budget_all.json 2> $O/bench_cfg2_budget_all.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_cfg2_driver_form.json 2> $O/bench_cfg2_driver_form.err
+for wl in cfg3 cfg1 cfg4; do python bench.py --full --workload $wl --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err; done
 bash tools/collect_profiles.sh $O/prof cfg1 cfg2 cfg3 cfg4 > $O/collect.log 2>&1
 python - <<'PY'
 import json, glob, os, sys
