@@ -383,6 +383,26 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg);
  * `stream`. */
 int64_t pgx_cost_to_go_builds(pgx_env* env, void* stream);
 
+/* Neighbour lists (docs/SPEC.md S12), read from the current device state -- the state the next pgx_step reads, which
+ * this call does not change.  With r = obs_radius, agent j is VISIBLE to agent i of the same env iff j != i, bit 0 of
+ * is_active[j] is set, and |dx| <= r and |dy| <= r for dx = x_j - x_i, dy = y_j - y_i: the square window of the
+ * observation; obstacles hide nobody, as in observation plane 1.  An agent whose own bit 0 is clear sees nobody.  The
+ * visible agents of i are ordered by the key (dx * dx + dy * dy, dx + r, dy + r, j), ascending, compared
+ * lexicographically: nearest first, ties in the row-major order of the window, then by agent index.
+ *   k       entries per agent, 1..PGX_MAX_NEIGHBOURS
+ *   flags   reserved, must be 0
+ *   index   device i32 [batch, agents, k]     the first min(count, k) visible agents in that order (agent index inside
+ *           the env), then -1.  Must not be NULL.
+ *   offset  device i8  [batch, agents, k, 2]  (dx, dy) of the same entries, (0, 0) where index is -1.  May be NULL.
+ *   count   device i32 [batch, agents]        the number of visible agents, NOT capped by k (count > k: the list was
+ *           truncated); 0 for an agent that is not active.  May be NULL.
+ * index and count must be 4-byte aligned, offset 2-byte aligned.  Replaces a [batch, agents, agents] distance
+ * broadcast and a top-k on the host side.  One kernel launch: allocates nothing (the first call included), asynchronous
+ * on `stream`, no host sync, capturable in a HIP graph.  PGX_E_INVALID for a k outside its range, non-zero flags, a
+ * NULL or misaligned output; PGX_E_STATE before the first reset, like pgx_step. */
+#define PGX_MAX_NEIGHBOURS 32
+int pgx_visible_agents(pgx_env* env, int32_t k, int32_t flags, int32_t* index, int8_t* offset, int32_t* count, void* stream);
+
 /* Number of out-of-range actions (outside 0..4) that ACTIVE agents submitted since the last call (bad_action =
  * PGX_BAD_ACTION_FLAG only; otherwise always 0).  Inactive agents' actions are never looked at, as in the reference's
  * `if self.grid.is_active[agent_idx]` guards.  Synchronises `stream`, then clears the counter.  The host side turns a

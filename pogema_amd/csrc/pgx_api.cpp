@@ -1048,6 +1048,32 @@ int64_t pgx_cost_to_go_builds(pgx_env* e, void* stream) {
     return (int64_t)n;
 }
 
+// ---- neighbour lists (docs/SPEC.md S12) -----------------------------------------------------------------
+int pgx_visible_agents(pgx_env* e, int32_t k, int32_t flags, int32_t* index, int8_t* offset, int32_t* count, void* stream) {
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_visible_agents", true)) return rc;
+    if (k < 1 || k > PGX_MAX_NEIGHBOURS)
+        return fail_msg(PGX_E_INVALID, "pgx_visible_agents: k = %d is outside 1..%d", k, PGX_MAX_NEIGHBOURS);
+    if (flags != 0) return fail_msg(PGX_E_INVALID, "pgx_visible_agents: flags must be 0, got 0x%x", flags);
+    if (!index) return fail_msg(PGX_E_INVALID, "pgx_visible_agents: index is null");
+    if ((reinterpret_cast<uintptr_t>(index) & 3) || (reinterpret_cast<uintptr_t>(count) & 3) ||
+        (reinterpret_cast<uintptr_t>(offset) & 1))
+        return fail_msg(PGX_E_INVALID, "pgx_visible_agents: index and count must be 4-byte aligned, offset 2-byte aligned");
+    const pgx::StepParams sp = step_params(e, e->geo);
+    pgx::NeighbourParams p{};
+    p.batch = sp.batch;
+    p.A = sp.num_agents;
+    p.r = sp.r;
+    p.k = k;
+    p.pos = sp.pos;
+    p.active = sp.active;
+    p.index = index;
+    p.offset = offset;
+    p.count = count;
+    PGX_HIP(pgx::launch_visible_agents(p, (hipStream_t)stream));
+    return PGX_OK;
+}
+
 int pgx_set_targets(pgx_env* e, const int32_t* target_xy, const uint8_t* agent_mask, void* stream) {
     if (!e || !target_xy) return fail_msg(PGX_E_INVALID, "pgx_set_targets: null argument");
     DeviceGuard guard;

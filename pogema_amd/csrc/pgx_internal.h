@@ -305,4 +305,16 @@ struct CostToGoParams {
 hipError_t prepare_cost_to_go(int H, int W);
 hipError_t launch_cost_to_go(const CostToGoParams& p, hipStream_t stream);
 
+// ---- neighbour lists (pgx_neighbours.hip) ---------------------------------------------------------------
+struct NeighbourParams {
+    int32_t batch, A, r;
+    int32_t k;               // entries per agent, 1..PGX_MAX_NEIGHBOURS
+    const uint32_t* pos;     // [B][A] (x << 16) | y, padded coordinates
+    const uint8_t* active;   // [B][A]
+    int32_t* index;          // [B][A][k]
+    int8_t* offset;          // [B][A][k][2], 2-byte aligned, may be null
+    int32_t* count;          // [B][A], may be null
+};
+hipError_t launch_visible_agents(const NeighbourParams& p, hipStream_t stream);
+
 }  // namespace pgx

@@ -184,6 +184,13 @@ class Pogema:
         w = self._vec.cost_to_go()[0].cpu().numpy()
         return [w[i] for i in range(w.shape[0])]
 
+    def visible_agents(self, k: int = 13):
+        """The agents each agent sees in its window (VecPogema.visible_agents): per agent a list of (j, dx, dy) tuples,
+        nearest first, truncated to `k`."""
+        index, offset, _ = (t[0].cpu().numpy() for t in self._vec.visible_agents(k=k))
+        return [[(int(j), int(d[0]), int(d[1])) for j, d in zip(index[i], offset[i]) if j >= 0]
+                for i in range(index.shape[0])]
+
     def _metrics_dict(self, values):
         from ._lib import METRIC_NAMES
         metrics = {k: float(x) for k, x in zip(METRIC_NAMES, values)}

@@ -885,6 +885,38 @@ class VecPogema(PlacementMixin):
             _lib.check(int(n))
         return int(n)
 
+    def visible_agents(self, k: int = 13, out=None):
+        """Neighbour lists (docs/SPEC.md S12), computed on the device from the current state -- the state the next
+        step() reads, which this call leaves untouched.  Agent j is visible to agent i of the same env iff j != i, j is
+        active and |dx| <= obs_radius and |dy| <= obs_radius for (dx, dy) = xy_j - xy_i (the square observation window;
+        obstacles hide nobody, as in observation plane 1); an inactive agent sees nobody.  The visible agents are ordered
+        by (dx * dx + dy * dy, dx + r, dy + r, j): nearest first, ties in the window's row-major order, then by index.
+        Returns (index int32 [batch, agents, k]: the first min(count, k) of them, then -1;
+                 offset int8 [batch, agents, k, 2]: their (dx, dy), (0, 0) where index is -1;
+                 count int32 [batch, agents]: the number of visible agents, not capped by k).
+        `k` is 1..MAX_NEIGHBOURS (32).  One kernel launch: allocates nothing on the engine side, stream-ordered, no host
+        sync, capturable in a HIP graph from the first call.  `out=(index, offset, count)`: caller-owned contiguous
+        tensors of those dtypes and shapes on this device."""
+        B, A = self.batch, self.num_agents
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _lib.MAX_NEIGHBOURS:
+            raise ValueError(f"k must be an integer in 1..{_lib.MAX_NEIGHBOURS}, got {k!r}")
+        k = int(k)
+        shapes = (("index", torch.int32, (B, A, k)), ("offset", torch.int8, (B, A, k, 2)), ("count", torch.int32, (B, A)))
+        if out is not None:
+            if len(out) != 3:
+                raise ValueError("out must be (index, offset, count)")
+            for t, (name, dtype, shape) in zip(out, shapes):
+                if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()
+                        or t.device != self.device or t.data_ptr() % t.element_size() or t.data_ptr() % 2):
+                    raise ValueError(f"out[{name}] must be a contiguous {dtype} tensor of shape {shape} on {self.device}"
+                                     + (" at an even address" if name == "offset" else ""))
+            index, offset, count = out
+        else:
+            index, offset, count = (torch.empty(shape, dtype=dtype, device=self.device) for _, dtype, shape in shapes)
+        _lib.check(self._lib.pgx_visible_agents(self._handle, k, 0, index.data_ptr(), offset.data_ptr(), count.data_ptr(),
+                                                self._stream()))
+        return index, offset, count
+
     def _wrap_obs(self, obs: torch.Tensor):
         """'default': the float32 tensor.  'POMAPF' / 'MAPF' (upstream `PogemaBase._pomapf_obs` / `_mapf_obs`):
         dict views over the same planes plus coordinates relative to each agent's start cell (and, for MAPF,
