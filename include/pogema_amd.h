@@ -379,8 +379,8 @@ int pgx_cost_to_go(pgx_env* env, int32_t flags, int32_t* out, void* stream);
  * rounded up to a multiple of 16 + 4 * B * A (target tags) + 4 * B * H * ceil(W / 32) (map copies).  Returns the status
  * code of pgx_check_config for a configuration it refuses. */
 int64_t pgx_cost_to_go_bytes(const pgx_config* cfg);
-/* Distance fields pgx_cost_to_go has built since the handle was created (0 before its first call).  Synchronises
- * `stream`. */
+/* Distance fields pgx_cost_to_go and pgx_pibt_actions have built since the handle was created (0 before the first call
+ * of either).  Synchronises `stream`. */
 int64_t pgx_cost_to_go_builds(pgx_env* env, void* stream);
 
 /* Neighbour lists (docs/SPEC.md S12), read from the current device state -- the state the next pgx_step reads, which
@@ -402,6 +402,31 @@ int64_t pgx_cost_to_go_builds(pgx_env* env, void* stream);
  * NULL or misaligned output; PGX_E_STATE before the first reset, like pgx_step. */
 #define PGX_MAX_NEIGHBOURS 32
 int pgx_visible_agents(pgx_env* env, int32_t k, int32_t flags, int32_t* index, int8_t* offset, int32_t* count, void* stream);
+
+/* Cooperative one-step planner (docs/SPEC.md S13): PIBT, priority inheritance with backtracking, read from the current
+ * device state -- the state the next pgx_step reads, which this call does not change.  An agent is PLANNED iff bit 0 of
+ * is_active is set.  Every planned agent gets a next cell among its own cell and its four neighbours (inside the
+ * height x width map, free of obstacles), preferred by the distance to its current target (pgx_cost_to_go's field of
+ * the agent; unreachable = infinite), then unoccupied before occupied, then the lower action.  Agents are served by
+ * (-priority, index); an agent that wants an occupied cell makes the cell's agent plan first (it inherits the turn) and
+ * takes its next candidate when that agent cannot move away.  No two planned agents share a next cell, no two swap
+ * cells.  Agents that are not planned get action 0 and their own cell; they occupy and reserve nothing.
+ *   flags     reserved, must be 0
+ *   priority  device i32 [batch, agents]; NULL: every priority is 0 (index order)
+ *   actions   device [batch, agents] of action_dtype (PGX_ACTION_*): 0 stay, 1..4 up, down, left, right.  Must not be
+ *             NULL.
+ *   next_xy   device i32 [batch, agents, 2]: the next cells, unpadded (row, col).  May be NULL.
+ * Under PGX_COLLISION_SOFT a pgx_step with these actions puts every planned agent on its next cell; under the other
+ * two collision systems a move into a cell another agent leaves in the same step may be reverted.
+ * Shares pgx_cost_to_go's distance-field cache: the call refreshes it (stale fields are rebuilt and counted by
+ * pgx_cost_to_go_builds) and then plans in one more launch.  Whichever of the two entry points is called first allocates
+ * the cache (pgx_cost_to_go_bytes() bytes), under pgx_cost_to_go's rules: inside a graph capture that first call
+ * returns PGX_E_STATE, a failed allocation returns PGX_E_NOMEM / PGX_E_HIP naming the bytes.  Afterwards asynchronous
+ * on `stream`, no host sync, capturable in a HIP graph.  PGX_E_INVALID for a NULL `actions`, non-zero flags, a bad
+ * action_dtype or a misaligned pointer (checked before the handle: no device needed); PGX_E_STATE before the first
+ * reset, like pgx_step. */
+int pgx_pibt_actions(pgx_env* env, int32_t flags, const int32_t* priority, void* actions, int32_t action_dtype,
+                     int32_t* next_xy, void* stream);
 
 /* Number of out-of-range actions (outside 0..4) that ACTIVE agents submitted since the last call (bad_action =
  * PGX_BAD_ACTION_FLAG only; otherwise always 0).  Inactive agents' actions are never looked at, as in the reference's

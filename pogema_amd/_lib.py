@@ -64,7 +64,7 @@ EXPORTED_SYMBOLS = (
     "pgx_buffers_create", "pgx_buffers_ptr", "pgx_buffers_get_info", "pgx_buffers_destroy", "pgx_set_targets",
     "pgx_np_streams", "pgx_np_streams_host", "pgx_np_generate", "pgx_np_generate_host", "pgx_rollout", "pgx_buffers_stride", "pgx_buffers_drop", "pgx_xcd_shares", "pgx_xcd_tune", "pgx_buffers_create_at", "pgx_time_observe_pair", "pgx_buffers_va_reserved", "pgx_get_geometry",
     "pgx_expert_actions", "pgx_set_map_pool", "pgx_reset_pool", "pgx_regenerate_pool", "pgx_get_map_index",
-    "pgx_cost_to_go", "pgx_cost_to_go_bytes", "pgx_cost_to_go_builds", "pgx_visible_agents",
+    "pgx_cost_to_go", "pgx_cost_to_go_bytes", "pgx_cost_to_go_builds", "pgx_visible_agents", "pgx_pibt_actions",
 )
 
 
@@ -182,6 +182,8 @@ def load() -> C.CDLL:
     lib.pgx_cost_to_go_builds.restype = i64
     lib.pgx_visible_agents.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.pgx_visible_agents.restype = C.c_int
+    lib.pgx_pibt_actions.argtypes = [vp, i32, vp, vp, i32, vp, vp]
+    lib.pgx_pibt_actions.restype = C.c_int
     lib.pgx_set_map_pool.argtypes = [vp, vp, i32, vp, vp]
     lib.pgx_set_map_pool.restype = C.c_int
     lib.pgx_reset_pool.argtypes = [vp, u64, vp, i32, vp]

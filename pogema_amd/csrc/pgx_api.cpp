@@ -103,7 +103,8 @@ struct pgx_env {
     DevBuf<uint32_t> pool_labels;         // [M][H*W] min-index component labels
     DevBuf<uint32_t> pool_cap;            // [M] start/target pairs each map can hold
     DevBuf<int32_t> map_index;            // [B] pool index of each env's map, -1 after a non-pool install
-    // cost-to-go cache (docs/SPEC.md S11, pgx::cost_to_go_layout), allocated by the first pgx_cost_to_go
+    // cost-to-go cache (docs/SPEC.md S11, pgx::cost_to_go_layout), allocated by the first pgx_cost_to_go or
+    // pgx_pibt_actions
     DevBuf<uint8_t> c2g;
 };
 
@@ -985,13 +986,10 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
     return (int64_t)pgx::cost_to_go_layout(cfg->batch, cfg->num_agents, cfg->height, cfg->width).bytes;
 }
 
-int pgx_cost_to_go(pgx_env* e, int32_t flags, int32_t* out, void* stream) {
-    if (!e || !out) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: null argument");
-    if (flags != 0) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: flags must be 0, got 0x%x", flags);
-    if (reinterpret_cast<uintptr_t>(out) & 3) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: out is not 4-byte aligned");
-    DeviceGuard guard;
-    if (const int rc = enter(guard, e, "pgx_cost_to_go", true)) return rc;
-    hipStream_t s = (hipStream_t)stream;
+// The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
+// first call of either entry point that uses it.  `who` names that entry point in the error messages.
+static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p,
+                            pgx::CostToGoLayout* out_l) {
     const pgx_config& c = e->cfg;
     const pgx::CostToGoLayout l = pgx::cost_to_go_layout(c.batch, c.num_agents, c.height, c.width);
     if (!e->c2g) {
@@ -999,13 +997,13 @@ int pgx_cost_to_go(pgx_env* e, int32_t flags, int32_t* out, void* stream) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         PGX_HIP(hipStreamIsCapturing(s, &cap));
         if (cap != hipStreamCaptureStatusNone)
-            return fail_msg(PGX_E_STATE, "pgx_cost_to_go: the first call allocates %zu bytes for the distance-field cache; "
-                                     "make it once outside graph capture", l.bytes);
+            return fail_msg(PGX_E_STATE, "%s: the first call allocates %zu bytes for the distance-field cache; "
+                                     "make it once outside graph capture", who, l.bytes);
         PGX_HIP(pgx::prepare_cost_to_go(c.height, c.width));
         const hipError_t err = e->c2g.alloc(l.bytes);
         if (err != hipSuccess) {
             (void)hipGetLastError();  // the failed allocation must not surface as the next launch's error
-            return fail_msg(alloc_code(err), "pgx_cost_to_go: distance-field cache of %zu bytes: %s", l.bytes,
+            return fail_msg(alloc_code(err), "%s: distance-field cache of %zu bytes: %s", who, l.bytes,
                             hipGetErrorString(err));
         }
         // no field, counter 0, an all-obstacle map copy (any installed map differs or leaves every tag cleared)
@@ -1014,7 +1012,7 @@ int pgx_cost_to_go(pgx_env* e, int32_t flags, int32_t* out, void* stream) {
         const hipError_t e2 = e1 != hipSuccess ? e1 : hipMemsetAsync(e->c2g + l.map_off, 0, l.bytes - l.map_off, s);
         if (e2 != hipSuccess) {
             e->c2g.reset();
-            return fail_msg(PGX_E_HIP, "pgx_cost_to_go: clearing the cache failed: %s", hipGetErrorString(e2));
+            return fail_msg(PGX_E_HIP, "%s: clearing the cache failed: %s", who, hipGetErrorString(e2));
         }
     }
     pgx::CostToGoParams p{};
@@ -1033,8 +1031,64 @@ int pgx_cost_to_go(pgx_env* e, int32_t flags, int32_t* out, void* stream) {
     p.tag = reinterpret_cast<uint32_t*>(e->c2g + l.tag_off);
     p.field = e->c2g + l.field_off;
     p.builds = reinterpret_cast<unsigned long long*>(e->c2g + l.builds_off);
+    *out_p = p;
+    *out_l = l;
+    return PGX_OK;
+}
+
+int pgx_cost_to_go(pgx_env* e, int32_t flags, int32_t* out, void* stream) {
+    if (!e || !out) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: null argument");
+    if (flags != 0) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: flags must be 0, got 0x%x", flags);
+    if (reinterpret_cast<uintptr_t>(out) & 3) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: out is not 4-byte aligned");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_cost_to_go", true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::CostToGoParams p{};
+    pgx::CostToGoLayout l{};
+    if (const int rc = cost_to_go_cache(e, s, "pgx_cost_to_go", &p, &l)) return rc;
     p.out = out;
     PGX_HIP(pgx::launch_cost_to_go(p, s));
+    return PGX_OK;
+}
+
+// ---- cooperative planner (docs/SPEC.md S13) --------------------------------------------------------------
+int pgx_pibt_actions(pgx_env* e, int32_t flags, const int32_t* priority, void* actions, int32_t action_dtype,
+                     int32_t* next_xy, void* stream) {
+    // the argument checks come first and need no device
+    if (!actions) return fail_msg(PGX_E_INVALID, "pgx_pibt_actions: actions is null");
+    if (flags != 0) return fail_msg(PGX_E_INVALID, "pgx_pibt_actions: flags must be 0, got 0x%x", flags);
+    if (action_dtype < 0 || action_dtype > 2)
+        return fail_msg(PGX_E_INVALID, "pgx_pibt_actions: bad action_dtype %d", action_dtype);
+    const uintptr_t action_align = action_dtype == PGX_ACTION_I8 ? 0 : action_dtype == PGX_ACTION_I32 ? 3 : 7;
+    if (reinterpret_cast<uintptr_t>(actions) & action_align)
+        return fail_msg(PGX_E_INVALID, "pgx_pibt_actions: actions is not aligned to its element size");
+    if ((reinterpret_cast<uintptr_t>(priority) & 3) || (reinterpret_cast<uintptr_t>(next_xy) & 3))
+        return fail_msg(PGX_E_INVALID, "pgx_pibt_actions: priority and next_xy must be 4-byte aligned");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_pibt_actions", true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::CostToGoParams cp{};
+    pgx::CostToGoLayout l{};
+    if (const int rc = cost_to_go_cache(e, s, "pgx_pibt_actions", &cp, &l)) return rc;
+    PGX_HIP(pgx::launch_cost_to_go_refresh(cp, s));
+    pgx::PibtParams p{};
+    p.batch = cp.batch;
+    p.A = cp.A;
+    p.H = cp.H;
+    p.W = cp.W;
+    p.r = cp.r;
+    p.wpr = cp.wpr;
+    p.bmw = cp.bmw;
+    p.action_dtype = action_dtype;
+    p.cell_bytes = (int32_t)l.cell_bytes;
+    p.obst = cp.obst;
+    p.pos = cp.pos;
+    p.active = cp.active;
+    p.field = cp.field;
+    p.priority = priority;
+    p.actions = actions;
+    p.next_xy = next_xy;
+    PGX_HIP(pgx::launch_pibt(p, s));
     return PGX_OK;
 }
 

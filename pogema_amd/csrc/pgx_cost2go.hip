@@ -352,7 +352,7 @@ hipError_t prepare_cost_to_go(int H, int W) {
     return raise_lds_limit(fn, c2g_large_lds(H, W));
 }
 
-hipError_t launch_cost_to_go(const CostToGoParams& p, hipStream_t stream) {
+hipError_t launch_cost_to_go_refresh(const CostToGoParams& p, hipStream_t stream) {
     const int wn = (p.W + 31) / 32;
     hipLaunchKernelGGL(c2g_invalidate_kernel, dim3(p.batch), dim3(256), 0, stream, p, wn);
     hipError_t err = hipGetLastError();
@@ -370,8 +370,14 @@ hipError_t launch_cost_to_go(const CostToGoParams& p, hipStream_t stream) {
         if (wide) hipLaunchKernelGGL(c2g_build_large_kernel<uint32_t>, dim3(grid), dim3(nt), lds, stream, p, per, wn, staged);
         else hipLaunchKernelGGL(c2g_build_large_kernel<uint16_t>, dim3(grid), dim3(nt), lds, stream, p, per, wn, staged);
     }
-    err = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launch_cost_to_go(const CostToGoParams& p, hipStream_t stream) {
+    const hipError_t err = launch_cost_to_go_refresh(p, stream);
     if (err != hipSuccess) return err;
+    const bool wide = c2g_wide_cells(p.H, p.W);
+    const size_t total = (size_t)p.batch * p.A;
     const int ws = 2 * p.r + 1;
     const size_t n = total * ws * ws;
     const size_t quads = (n + 3) / 4;

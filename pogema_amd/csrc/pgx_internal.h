@@ -303,6 +303,9 @@ struct CostToGoParams {
     int32_t* out;            // [B][A][2r+1][2r+1]
 };
 hipError_t prepare_cost_to_go(int H, int W);
+// invalidate + build: every active agent's field is valid for its current target afterwards (`out` is not used)
+hipError_t launch_cost_to_go_refresh(const CostToGoParams& p, hipStream_t stream);
+// the refresh, then the gather of the windows into `out`
 hipError_t launch_cost_to_go(const CostToGoParams& p, hipStream_t stream);
 
 // ---- neighbour lists (pgx_neighbours.hip) ---------------------------------------------------------------
@@ -316,5 +319,20 @@ struct NeighbourParams {
     int32_t* count;          // [B][A], may be null
 };
 hipError_t launch_visible_agents(const NeighbourParams& p, hipStream_t stream);
+
+// ---- cooperative planner (pgx_pibt.hip) ---------------------------------------------------------------------
+struct PibtParams {
+    int32_t batch, A, H, W, r, wpr, bmw;
+    int32_t action_dtype;    // PGX_ACTION_*
+    int32_t cell_bytes;      // of `field`: CostToGoLayout::cell_bytes
+    const uint32_t* obst;    // [B][bmw] padded obstacle bitmaps
+    const uint32_t* pos;     // [B][A]
+    const uint8_t* active;   // [B][A]
+    const void* field;       // [B][A][H*W] the refreshed distance fields of the cost-to-go cache
+    const int32_t* priority; // [B][A], null: every priority is 0
+    void* actions;           // [B][A] of action_dtype
+    int32_t* next_xy;        // [B][A][2] unpadded, may be null
+};
+hipError_t launch_pibt(const PibtParams& p, hipStream_t stream);
 
 }  // namespace pgx

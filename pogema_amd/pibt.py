@@ -1,0 +1,31 @@
+"""PibtPolicy: the cooperative planner (VecPogema.pibt_actions, docs/SPEC.md S13) with the textbook dynamic priorities --
+an agent's priority grows by one every step it has not reached its target and drops to zero when it has, so that an
+agent that keeps being pushed aside eventually outranks its neighbours."""
+from __future__ import annotations
+
+import torch
+
+
+class PibtPolicy:
+    """`act()` -> (actions, next_xy) for `env.step`; `update(rewards, episode_done)` after the step.  The int32 priority
+    tensor [batch, agents] lives on the env's device; nothing here synchronises with the host."""
+
+    def __init__(self, env):
+        self.env = env
+        self.priority = torch.zeros((env.batch, env.num_agents), dtype=torch.int32, device=env.device)
+
+    def reset(self) -> None:
+        self.priority.zero_()
+
+    def act(self, dtype=torch.int64, out=None):
+        return self.env.pibt_actions(priority=self.priority, dtype=dtype, out=out)
+
+    def update(self, rewards, episode_done=None) -> None:
+        """Priority becomes 0 where the agent got a positive reward in this step, stands on its target, is inactive, or
+        its env's episode finished (`episode_done`: bool / uint8 [batch], e.g. step()'s infos["episode_done"]);
+        everywhere else it goes up by 1."""
+        st = self.env.get_state()
+        zero = (rewards > 0) | (st["agents_xy"] == st["targets_xy"]).all(dim=-1) | ~st["is_active"]
+        if episode_done is not None:
+            zero = zero | episode_done.to(torch.bool).view(-1, 1)
+        self.priority = torch.where(zero, torch.zeros_like(self.priority), self.priority + 1)

@@ -879,7 +879,7 @@ class VecPogema(PlacementMixin):
 
     @property
     def cost_to_go_builds(self) -> int:
-        """Distance fields cost_to_go() has built since this env was created (synchronises the stream)."""
+        """Distance fields cost_to_go() and pibt_actions() have built since this env was created (synchronises the stream)."""
         n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
         if n < 0:
             _lib.check(int(n))
@@ -916,6 +916,49 @@ class VecPogema(PlacementMixin):
         _lib.check(self._lib.pgx_visible_agents(self._handle, k, 0, index.data_ptr(), offset.data_ptr(), count.data_ptr(),
                                                 self._stream()))
         return index, offset, count
+
+    def pibt_actions(self, priority=None, dtype=torch.int64, out=None):
+        """Cooperative one-step planner (PIBT, docs/SPEC.md S13), computed on the device from the current state -- the
+        state the next step() reads, which this call leaves untouched.  Returns (actions [batch, agents] of `dtype`,
+        next_xy int32 [batch, agents, 2]: the cell each agent is sent to, unpadded (row, col)).  Every active agent gets
+        one of its own cell and its free neighbours, preferred by the distance to its target (cost_to_go()'s fields),
+        agents served by (-priority, index), with priority inheritance and backtracking: no two active agents get the
+        same cell and no two swap.  Inactive agents get action 0 and their own cell.  Under collision_system="soft"
+        step(actions) puts every active agent on its next_xy; under "priority" and "block_both" a move into a cell that
+        another agent leaves in the same step may be reverted.
+        `priority`: an integer tensor [batch, agents] on this device (converted to int32), None = all equal.
+        Shares cost_to_go()'s cache: whichever is called first allocates it (not inside a graph capture); later calls are
+        stream-ordered, need no host sync and can be captured.  `out=(actions, next_xy)`: caller-owned contiguous
+        tensors on this device (actions int8 / int32 / int64, next_xy int32)."""
+        B, A = self.batch, self.num_agents
+        if priority is not None:
+            if not isinstance(priority, torch.Tensor):
+                raise TypeError(f"priority must be a torch.Tensor or None, got {type(priority).__name__}")
+            if priority.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
+                raise TypeError(f"priority must be an integer tensor, got {priority.dtype}")
+            if tuple(priority.shape) != (B, A) or priority.device != self.device:
+                raise ValueError(f"priority must have shape {(B, A)} on {self.device}")
+            priority = priority.to(torch.int32).contiguous()
+        if out is not None:
+            if len(out) != 2:
+                raise ValueError("out must be (actions, next_xy)")
+            actions, next_xy = out
+            if (not isinstance(actions, torch.Tensor) or actions.dtype not in self._ACTION_CODE
+                    or tuple(actions.shape) != (B, A) or not actions.is_contiguous() or actions.device != self.device):
+                raise ValueError(f"out[actions] must be a contiguous int8 / int32 / int64 tensor of shape {(B, A)} on "
+                                 f"{self.device}")
+            if (not isinstance(next_xy, torch.Tensor) or next_xy.dtype != torch.int32 or tuple(next_xy.shape) != (B, A, 2)
+                    or not next_xy.is_contiguous() or next_xy.device != self.device):
+                raise ValueError(f"out[next_xy] must be a contiguous int32 tensor of shape {(B, A, 2)} on {self.device}")
+        else:
+            if dtype not in self._ACTION_CODE:
+                raise ValueError(f"dtype must be one of torch.int8, torch.int32, torch.int64, got {dtype}")
+            actions = torch.empty((B, A), dtype=dtype, device=self.device)
+            next_xy = torch.empty((B, A, 2), dtype=torch.int32, device=self.device)
+        _lib.check(self._lib.pgx_pibt_actions(self._handle, 0, priority.data_ptr() if priority is not None else None,
+                                              actions.data_ptr(), self._ACTION_CODE[actions.dtype], next_xy.data_ptr(),
+                                              self._stream()))
+        return actions, next_xy
 
     def _wrap_obs(self, obs: torch.Tensor):
         """'default': the float32 tensor.  'POMAPF' / 'MAPF' (upstream `PogemaBase._pomapf_obs` / `_mapf_obs`):
