@@ -379,8 +379,8 @@ int pgx_cost_to_go(pgx_env* env, int32_t flags, int32_t* out, void* stream);
  * rounded up to a multiple of 16 + 4 * B * A (target tags) + 4 * B * H * ceil(W / 32) (map copies).  Returns the status
  * code of pgx_check_config for a configuration it refuses. */
 int64_t pgx_cost_to_go_bytes(const pgx_config* cfg);
-/* Distance fields pgx_cost_to_go and pgx_pibt_actions have built since the handle was created (0 before the first call
- * of either).  Synchronises `stream`. */
+/* Distance fields pgx_cost_to_go, pgx_pibt_actions and pgx_goal_directions have built since the handle was created (0
+ * before the first call of any of them).  Synchronises `stream`. */
 int64_t pgx_cost_to_go_builds(pgx_env* env, void* stream);
 
 /* Neighbour lists (docs/SPEC.md S12), read from the current device state -- the state the next pgx_step reads, which
@@ -419,14 +419,44 @@ int pgx_visible_agents(pgx_env* env, int32_t k, int32_t flags, int32_t* index, i
  * Under PGX_COLLISION_SOFT a pgx_step with these actions puts every planned agent on its next cell; under the other
  * two collision systems a move into a cell another agent leaves in the same step may be reverted.
  * Shares pgx_cost_to_go's distance-field cache: the call refreshes it (stale fields are rebuilt and counted by
- * pgx_cost_to_go_builds) and then plans in one more launch.  Whichever of the two entry points is called first allocates
- * the cache (pgx_cost_to_go_bytes() bytes), under pgx_cost_to_go's rules: inside a graph capture that first call
+ * pgx_cost_to_go_builds) and then plans in one more launch.  Whichever entry point that uses the cache is called first allocates
+ * it (pgx_cost_to_go_bytes() bytes), under pgx_cost_to_go's rules: inside a graph capture that first call
  * returns PGX_E_STATE, a failed allocation returns PGX_E_NOMEM / PGX_E_HIP naming the bytes.  Afterwards asynchronous
  * on `stream`, no host sync, capturable in a HIP graph.  PGX_E_INVALID for a NULL `actions`, non-zero flags, a bad
  * action_dtype or a misaligned pointer (checked before the handle: no device needed); PGX_E_STATE before the first
  * reset, like pgx_step. */
 int pgx_pibt_actions(pgx_env* env, int32_t flags, const int32_t* priority, void* actions, int32_t action_dtype,
                      int32_t* next_xy, void* stream);
+
+/* Direction-to-goal planes (docs/SPEC.md S14), the "heuristic channels" of learned MAPF policies, read from the current
+ * device state -- the state the next pgx_step reads, which this call does not change.  For every agent, window cell
+ * (u, v) = map cell c = (x - r + u, y - r + v) in the orientation of observation plane 0, and move a of 1..4 (up, down,
+ * left, right): plane a - 1 is 1 at (u, v) iff the distance of c to the agent's current target (pgx_cost_to_go's field)
+ * is defined and the distance of the cell move a leads to from c is defined and smaller.  That cell may lie outside the
+ * window: it is looked up in the field all the same, which is what pgx_cost_to_go's windows cannot give.  All four
+ * planes are 0 on the target cell, wherever pgx_cost_to_go gives -1 (outside the map, obstacles, cells not connected to
+ * the target, every cell when the target is an obstacle) and for an agent that is not active (bit 0 of is_active
+ * clear).  Other agents are not obstacles.  The lowest plane set at the window centre is pgx_expert_actions' action
+ * without PGX_EXPERT_AGENTS_AS_OBSTACLES.
+ *   flags   reserved, must be 0
+ *   out     device buffer, must not be NULL, of `format`:
+ *           PGX_DIRECTIONS_F32   f32 [batch, agents, 4, 2r+1, 2r+1]  0.0 / 1.0 (4-byte aligned)
+ *           PGX_DIRECTIONS_U8    u8  [batch, agents, 4, 2r+1, 2r+1]  0 / 1
+ *           PGX_DIRECTIONS_BITS  u8  [batch, agents, 2r+1, 2r+1]     bit a - 1 = plane a - 1, bits 4..7 zero
+ *           Any alignment beyond that is accepted, at a price: a 16-byte aligned `out` is written with 16-byte
+ *           stores, any other with one store per element (per byte for the two u8 formats), which is markedly
+ *           slower.  Keep `out` 16-byte aligned on a hot path (a fresh device allocation is).
+ * Shares pgx_cost_to_go's distance-field cache: the call refreshes it (stale fields are rebuilt and counted by
+ * pgx_cost_to_go_builds) and then gathers in one more launch.  Whichever of pgx_cost_to_go, pgx_pibt_actions and this
+ * entry point is called first allocates the cache (pgx_cost_to_go_bytes() bytes), under pgx_cost_to_go's rules: inside a
+ * graph capture that first call returns PGX_E_STATE, a failed allocation returns PGX_E_NOMEM / PGX_E_HIP naming the
+ * bytes.  Afterwards asynchronous on `stream`, no host sync, capturable in a HIP graph.  PGX_E_INVALID for non-zero
+ * flags, a NULL `out`, an unknown format or a misaligned float32 `out` (checked before the handle: no device needed);
+ * PGX_E_STATE before the first reset, like pgx_step. */
+#define PGX_DIRECTIONS_F32 0
+#define PGX_DIRECTIONS_U8 1
+#define PGX_DIRECTIONS_BITS 2
+int pgx_goal_directions(pgx_env* env, int32_t flags, void* out, int32_t format, void* stream);
 
 /* Number of out-of-range actions (outside 0..4) that ACTIVE agents submitted since the last call (bad_action =
  * PGX_BAD_ACTION_FLAG only; otherwise always 0).  Inactive agents' actions are never looked at, as in the reference's

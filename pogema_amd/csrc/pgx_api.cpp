@@ -103,8 +103,8 @@ struct pgx_env {
     DevBuf<uint32_t> pool_labels;         // [M][H*W] min-index component labels
     DevBuf<uint32_t> pool_cap;            // [M] start/target pairs each map can hold
     DevBuf<int32_t> map_index;            // [B] pool index of each env's map, -1 after a non-pool install
-    // cost-to-go cache (docs/SPEC.md S11, pgx::cost_to_go_layout), allocated by the first pgx_cost_to_go or
-    // pgx_pibt_actions
+    // cost-to-go cache (docs/SPEC.md S11, pgx::cost_to_go_layout), allocated by the first pgx_cost_to_go,
+    // pgx_pibt_actions or pgx_goal_directions
     DevBuf<uint8_t> c2g;
 };
 
@@ -987,7 +987,7 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
 }
 
 // The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
-// first call of either entry point that uses it.  `who` names that entry point in the error messages.
+// first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_goal_directions).  `who` names that entry point in the error messages.
 static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p,
                             pgx::CostToGoLayout* out_l) {
     const pgx_config& c = e->cfg;
@@ -1089,6 +1089,27 @@ int pgx_pibt_actions(pgx_env* e, int32_t flags, const int32_t* priority, void* a
     p.actions = actions;
     p.next_xy = next_xy;
     PGX_HIP(pgx::launch_pibt(p, s));
+    return PGX_OK;
+}
+
+// ---- direction-to-goal planes (docs/SPEC.md S14) ----------------------------------------------------------
+int pgx_goal_directions(pgx_env* e, int32_t flags, void* out, int32_t format, void* stream) {
+    // the argument checks come first and need no device
+    if (!out) return fail_msg(PGX_E_INVALID, "pgx_goal_directions: out is null");
+    if (flags != 0) return fail_msg(PGX_E_INVALID, "pgx_goal_directions: flags must be 0, got 0x%x", flags);
+    static_assert(PGX_DIRECTIONS_F32 == pgx::DIRECTIONS_F32 && PGX_DIRECTIONS_U8 == pgx::DIRECTIONS_U8 &&
+                      PGX_DIRECTIONS_BITS == pgx::DIRECTIONS_BITS, "the kernels' format codes are the header's");
+    if (format != PGX_DIRECTIONS_F32 && format != PGX_DIRECTIONS_U8 && format != PGX_DIRECTIONS_BITS)
+        return fail_msg(PGX_E_INVALID, "pgx_goal_directions: bad format %d", format);
+    if (format == PGX_DIRECTIONS_F32 && (reinterpret_cast<uintptr_t>(out) & 3))
+        return fail_msg(PGX_E_INVALID, "pgx_goal_directions: a float32 out must be 4-byte aligned");
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_goal_directions", true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::CostToGoParams p{};
+    pgx::CostToGoLayout l{};
+    if (const int rc = cost_to_go_cache(e, s, "pgx_goal_directions", &p, &l)) return rc;
+    PGX_HIP(pgx::launch_goal_directions(p, l.cell_bytes, out, format, s));
     return PGX_OK;
 }
 

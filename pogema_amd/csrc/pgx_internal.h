@@ -308,6 +308,12 @@ hipError_t launch_cost_to_go_refresh(const CostToGoParams& p, hipStream_t stream
 // the refresh, then the gather of the windows into `out`
 hipError_t launch_cost_to_go(const CostToGoParams& p, hipStream_t stream);
 
+// ---- direction-to-goal planes (pgx_directions.hip) ---------------------------------------------------------
+enum { DIRECTIONS_F32 = 0, DIRECTIONS_U8 = 1, DIRECTIONS_BITS = 2 };  // PGX_DIRECTIONS_* (include/pogema_amd.h)
+// the refresh of the cost-to-go cache `p` describes (`p.out` is not used), then the planes of every agent into `out`:
+// [B][A][4][2r+1][2r+1] float32 or u8, or [B][A][2r+1][2r+1] u8 masks; cell_bytes: CostToGoLayout::cell_bytes
+hipError_t launch_goal_directions(const CostToGoParams& p, size_t cell_bytes, void* out, int format, hipStream_t stream);
+
 // ---- neighbour lists (pgx_neighbours.hip) ---------------------------------------------------------------
 struct NeighbourParams {
     int32_t batch, A, r;

@@ -184,6 +184,12 @@ class Pogema:
         w = self._vec.cost_to_go()[0].cpu().numpy()
         return [w[i] for i in range(w.shape[0])]
 
+    def goal_directions(self):
+        """The direction-to-goal planes of every agent (VecPogema.goal_directions) as a list of uint8 (4, W, W) numpy
+        arrays."""
+        d = self._vec.goal_directions(format="uint8")[0].cpu().numpy()
+        return [d[i] for i in range(d.shape[0])]
+
     def visible_agents(self, k: int = 13):
         """The agents each agent sees in its window (VecPogema.visible_agents): per agent a list of (j, dx, dy) tuples,
         nearest first, truncated to `k`."""

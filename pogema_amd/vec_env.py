@@ -879,7 +879,8 @@ class VecPogema(PlacementMixin):
 
     @property
     def cost_to_go_builds(self) -> int:
-        """Distance fields cost_to_go() and pibt_actions() have built since this env was created (synchronises the stream)."""
+        """Distance fields cost_to_go(), pibt_actions() and goal_directions() have built since this env was created
+        (synchronises the stream)."""
         n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
         if n < 0:
             _lib.check(int(n))
@@ -959,6 +960,35 @@ class VecPogema(PlacementMixin):
                                               actions.data_ptr(), self._ACTION_CODE[actions.dtype], next_xy.data_ptr(),
                                               self._stream()))
         return actions, next_xy
+
+    def goal_directions(self, format: str = "float32", out=None) -> torch.Tensor:
+        """Direction-to-goal planes (docs/SPEC.md S14), the "heuristic channels" of DHC-style policies, computed on the
+        device from the current state -- the state the next step() reads, which this call leaves untouched.  Plane
+        a - 1 of an agent's window (W = 2 * obs_radius + 1, the orientation of observation plane 0) is 1 at a cell iff
+        move a (1..4: up, down, left, right) from that cell leads to a cell strictly closer to the agent's target; the
+        cell moved to is looked up in the agent's whole distance field, so the window's edge is exact.  All four are 0
+        on the target, wherever cost_to_go() gives -1 and for inactive agents.  The lowest plane set at the centre is
+        expert_actions()' action.
+        `format`: "float32" -> float32 [batch, agents, 4, W, W] of 0.0 / 1.0, ready for torch.cat behind the observation;
+                  "uint8"   -> uint8 [batch, agents, 4, W, W] of 0 / 1;
+                  "bits"    -> uint8 [batch, agents, W, W], bit a - 1 = plane a - 1.
+        Shares cost_to_go()'s cache: whichever of cost_to_go(), pibt_actions() and this is called first allocates it
+        (not inside a graph capture); later calls are stream-ordered, need no host sync and can be captured.  `out`: a
+        caller-owned contiguous tensor of that dtype and shape on this device."""
+        if format not in _lib.DIRECTIONS_FORMATS:
+            raise ValueError(f"format must be one of {sorted(_lib.DIRECTIONS_FORMATS)}, got {format!r}")
+        dtype = torch.float32 if format == "float32" else torch.uint8
+        planes = () if format == "bits" else (4,)
+        shape = (self.batch, self.num_agents) + planes + (self.window, self.window)
+        if out is not None:
+            if (not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape
+                    or not out.is_contiguous() or out.device != self.device):
+                raise ValueError(f"out must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+        else:
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        _lib.check(self._lib.pgx_goal_directions(self._handle, 0, out.data_ptr(), _lib.DIRECTIONS_FORMATS[format],
+                                                 self._stream()))
+        return out
 
     def _wrap_obs(self, obs: torch.Tensor):
         """'default': the float32 tensor.  'POMAPF' / 'MAPF' (upstream `PogemaBase._pomapf_obs` / `_mapf_obs`):
