@@ -61,6 +61,36 @@ struct DevBuf {
 
 int alloc_code(hipError_t err) { return err == hipErrorOutOfMemory ? PGX_E_NOMEM : PGX_E_HIP; }
 
+// The allocation of `buf` (`bytes` of `what`) by the first call of entry point `who` that needs it, so that callers who
+// never ask never pay for it.  PGX_E_STATE while `s` is capturing; the failed allocation must not surface as the next
+// launch's error.
+template <class T>
+int alloc_on_first_use(DevBuf<T>& buf, size_t bytes, hipStream_t s, const char* who, const char* what) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    PGX_HIP(hipStreamIsCapturing(s, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return fail_msg(PGX_E_STATE, "%s: the first call allocates %zu bytes for %s; make it once outside graph capture",
+                        who, bytes, what);
+    const hipError_t err = buf.alloc(bytes);
+    if (err == hipSuccess) return PGX_OK;
+    (void)hipGetLastError();
+    return fail_msg(alloc_code(err), "%s: %s of %zu bytes: %s", who, what, bytes, hipGetErrorString(err));
+}
+
+// The argument checks the entry points share: PGX_OK, or PGX_E_INVALID with a message naming `who` and the argument.
+int check_aligned(const char* who, const char* name, const void* p, size_t n) {  // n: a power of two
+    if (reinterpret_cast<uintptr_t>(p) & (n - 1)) return fail_msg(PGX_E_INVALID, "%s: %s is not %zu-byte aligned", who, name, n);
+    return PGX_OK;
+}
+int check_action_dtype(const char* who, int32_t action_dtype) {
+    if (action_dtype < 0 || action_dtype > 2) return fail_msg(PGX_E_INVALID, "%s: bad action_dtype %d", who, action_dtype);
+    return PGX_OK;
+}
+int check_flags(const char* who, int32_t flags, int32_t known) {
+    if (flags & ~known) return fail_msg(PGX_E_INVALID, known ? "%s: unknown flags 0x%x" : "%s: flags must be 0, got 0x%x", who, flags);
+    return PGX_OK;
+}
+
 }  // namespace
 
 struct pgx_env {
@@ -186,6 +216,12 @@ pgx::StepParams observe_params(const pgx_env* e, void* obs) {
     p.mode = pgx::MODE_OBSERVE;
     p.obs = static_cast<float*>(obs);
     return p;
+}
+
+// What the read-only queries see of the handle's state.
+pgx::StateView state_view(const pgx_env* e) {
+    const pgx_config& c = e->cfg;
+    return {c.batch, c.num_agents, c.height, c.width, c.obs_radius, e->wpr, e->bmw, e->obst, e->pos, e->tgt, e->active};
 }
 
 // Mean time of one launch of `p` in us: `warmup` launches, then `timed` launches between an event pair; launch i of
@@ -871,7 +907,7 @@ int pgx_get_map(pgx_env* e, uint8_t* obstacles, void* stream) {
 int pgx_step(pgx_env* e, const void* actions, int action_dtype, void* obs, float* rewards, uint8_t* terminated,
              uint8_t* truncated, uint8_t* is_active, void* stream) {
     if (!e || !actions || !rewards || !terminated || !truncated) return fail_msg(PGX_E_INVALID, "pgx_step: null argument");
-    if (action_dtype < 0 || action_dtype > 2) return fail_msg(PGX_E_INVALID, "pgx_step: bad action_dtype %d", action_dtype);
+    if (const int rc = check_action_dtype("pgx_step", action_dtype)) return rc;
     DeviceGuard guard;
     if (const int rc = enter(guard, e, "pgx_step", true)) return rc;
     pgx::StepParams p = step_params(e, e->geo);
@@ -893,7 +929,7 @@ int pgx_rollout(pgx_env* e, int32_t steps, const pgx_rollout_io* io, void* strea
     if (io->policy_step0 < 0 || io->policy_step0 > ((int64_t)1 << 40))
         return fail_msg(PGX_E_INVALID, "pgx_rollout: policy_step0 outside 0..2^40");
     if (steps < 1) return fail_msg(PGX_E_INVALID, "pgx_rollout: steps must be >= 1, got %d", steps);
-    if (io->action_dtype < 0 || io->action_dtype > 2) return fail_msg(PGX_E_INVALID, "pgx_rollout: bad action_dtype %d", io->action_dtype);
+    if (const int rc = check_action_dtype("pgx_rollout", io->action_dtype)) return rc;
     if (io->obs && io->obs_slots < 1) return fail_msg(PGX_E_INVALID, "pgx_rollout: obs given but obs_slots = %d", io->obs_slots);
     DeviceGuard guard;
     if (const int rc = enter(guard, e, "pgx_rollout", true)) return rc;
@@ -934,41 +970,22 @@ int pgx_rollout(pgx_env* e, int32_t steps, const pgx_rollout_io* io, void* strea
 }
 
 int pgx_expert_actions(pgx_env* e, int32_t flags, void* actions, int32_t action_dtype, int32_t* distance, void* stream) {
-    if (!e || !actions) return fail_msg(PGX_E_INVALID, "pgx_expert_actions: null argument");
-    if (action_dtype < 0 || action_dtype > 2)
-        return fail_msg(PGX_E_INVALID, "pgx_expert_actions: bad action_dtype %d", action_dtype);
-    if (flags & ~PGX_EXPERT_AGENTS_AS_OBSTACLES) return fail_msg(PGX_E_INVALID, "pgx_expert_actions: unknown flags 0x%x", flags);
+    static const char who[] = "pgx_expert_actions";
+    if (!e || !actions) return fail_msg(PGX_E_INVALID, "%s: null argument", who);
+    if (const int rc = check_action_dtype(who, action_dtype)) return rc;
+    if (const int rc = check_flags(who, flags, PGX_EXPERT_AGENTS_AS_OBSTACLES)) return rc;
     DeviceGuard guard;
-    if (const int rc = enter(guard, e, "pgx_expert_actions", true)) return rc;
+    if (const int rc = enter(guard, e, who, true)) return rc;
     const bool with_agents = (flags & PGX_EXPERT_AGENTS_AS_OBSTACLES) != 0;
     const size_t occ_words = pgx::expert_occupancy_words(e->cfg.batch, e->cfg.height, e->cfg.width);
-    if (with_agents && occ_words && !e->expert_occ) {
-        // the large-map layout's occupancy scratch: allocated on first use, so that step-only callers never pay for it
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        PGX_HIP(hipStreamIsCapturing((hipStream_t)stream, &cap));
-        if (cap != hipStreamCaptureStatusNone)
-            return fail_msg(PGX_E_STATE, "pgx_expert_actions: the first call with PGX_EXPERT_AGENTS_AS_OBSTACLES on maps wider or "
-                                     "taller than 64 allocates %zu bytes of scratch; make it once outside graph capture",
-                            occ_words * sizeof(uint32_t));
-        const hipError_t err = e->expert_occ.alloc(occ_words * sizeof(uint32_t));
-        if (err != hipSuccess)
-            return fail_msg(alloc_code(err), "pgx_expert_actions: occupancy scratch of %zu bytes: %s",
-                            occ_words * sizeof(uint32_t), hipGetErrorString(err));
-    }
-    pgx::ExpertParams p{};
-    p.batch = e->cfg.batch;
-    p.A = e->cfg.num_agents;
-    p.H = e->cfg.height;
-    p.W = e->cfg.width;
-    p.r = e->cfg.obs_radius;
-    p.wpr = e->wpr;
-    p.bmw = e->bmw;
+    if (with_agents && occ_words && !e->expert_occ)
+        if (const int rc = alloc_on_first_use(e->expert_occ, occ_words * sizeof(uint32_t), (hipStream_t)stream, who,
+                                              "the occupancy scratch of PGX_EXPERT_AGENTS_AS_OBSTACLES on maps wider "
+                                              "or taller than 64"))
+            return rc;
+    pgx::ExpertParams p{state_view(e)};
     p.with_agents = with_agents ? 1 : 0;
     p.action_dtype = action_dtype;
-    p.obst = e->obst;
-    p.pos = e->pos;
-    p.tgt = e->tgt;
-    p.active = e->active;
     p.occ = e->expert_occ;
     p.actions = actions;
     p.distance = distance;
@@ -987,65 +1004,43 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
 }
 
 // The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
-// first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_goal_directions).  `who` names that entry point in the error messages.
-static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p,
-                            pgx::CostToGoLayout* out_l) {
+// first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_goal_directions).  `who` names that
+// entry point in the error messages.
+static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p) {
     const pgx_config& c = e->cfg;
     const pgx::CostToGoLayout l = pgx::cost_to_go_layout(c.batch, c.num_agents, c.height, c.width);
     if (!e->c2g) {
-        // the cache: allocated on first use, so that callers who never ask for windows never pay for it
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        PGX_HIP(hipStreamIsCapturing(s, &cap));
-        if (cap != hipStreamCaptureStatusNone)
-            return fail_msg(PGX_E_STATE, "%s: the first call allocates %zu bytes for the distance-field cache; "
-                                     "make it once outside graph capture", who, l.bytes);
         PGX_HIP(pgx::prepare_cost_to_go(c.height, c.width));
-        const hipError_t err = e->c2g.alloc(l.bytes);
-        if (err != hipSuccess) {
-            (void)hipGetLastError();  // the failed allocation must not surface as the next launch's error
-            return fail_msg(alloc_code(err), "%s: distance-field cache of %zu bytes: %s", who, l.bytes,
-                            hipGetErrorString(err));
-        }
+        if (const int rc = alloc_on_first_use(e->c2g, l.bytes, s, who, "the distance-field cache")) return rc;
         // no field, counter 0, an all-obstacle map copy (any installed map differs or leaves every tag cleared)
-        const hipError_t e0 = hipMemsetAsync(e->c2g, 0, l.field_off, s);
-        const hipError_t e1 = e0 != hipSuccess ? e0 : hipMemsetAsync(e->c2g + l.tag_off, 0xFF, l.map_off - l.tag_off, s);
-        const hipError_t e2 = e1 != hipSuccess ? e1 : hipMemsetAsync(e->c2g + l.map_off, 0, l.bytes - l.map_off, s);
-        if (e2 != hipSuccess) {
+        hipError_t err = hipMemsetAsync(e->c2g, 0, l.field_off, s);
+        if (err == hipSuccess) err = hipMemsetAsync(e->c2g + l.tag_off, 0xFF, l.map_off - l.tag_off, s);
+        if (err == hipSuccess) err = hipMemsetAsync(e->c2g + l.map_off, 0, l.bytes - l.map_off, s);
+        if (err != hipSuccess) {
             e->c2g.reset();
-            return fail_msg(PGX_E_HIP, "%s: clearing the cache failed: %s", who, hipGetErrorString(e2));
+            return fail_msg(PGX_E_HIP, "%s: clearing the cache failed: %s", who, hipGetErrorString(err));
         }
     }
-    pgx::CostToGoParams p{};
-    p.batch = c.batch;
-    p.A = c.num_agents;
-    p.H = c.height;
-    p.W = c.width;
-    p.r = c.obs_radius;
-    p.wpr = e->wpr;
-    p.bmw = e->bmw;
-    p.obst = e->obst;
-    p.pos = e->pos;
-    p.tgt = e->tgt;
-    p.active = e->active;
+    pgx::CostToGoParams p{state_view(e)};
+    p.cell_bytes = (int32_t)l.cell_bytes;
     p.map_bits = reinterpret_cast<uint32_t*>(e->c2g + l.map_off);
     p.tag = reinterpret_cast<uint32_t*>(e->c2g + l.tag_off);
     p.field = e->c2g + l.field_off;
     p.builds = reinterpret_cast<unsigned long long*>(e->c2g + l.builds_off);
     *out_p = p;
-    *out_l = l;
     return PGX_OK;
 }
 
 int pgx_cost_to_go(pgx_env* e, int32_t flags, int32_t* out, void* stream) {
-    if (!e || !out) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: null argument");
-    if (flags != 0) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: flags must be 0, got 0x%x", flags);
-    if (reinterpret_cast<uintptr_t>(out) & 3) return fail_msg(PGX_E_INVALID, "pgx_cost_to_go: out is not 4-byte aligned");
+    static const char who[] = "pgx_cost_to_go";
+    if (!e || !out) return fail_msg(PGX_E_INVALID, "%s: null argument", who);
+    if (const int rc = check_flags(who, flags, 0)) return rc;
+    if (const int rc = check_aligned(who, "out", out, 4)) return rc;
     DeviceGuard guard;
-    if (const int rc = enter(guard, e, "pgx_cost_to_go", true)) return rc;
+    if (const int rc = enter(guard, e, who, true)) return rc;
     hipStream_t s = (hipStream_t)stream;
     pgx::CostToGoParams p{};
-    pgx::CostToGoLayout l{};
-    if (const int rc = cost_to_go_cache(e, s, "pgx_cost_to_go", &p, &l)) return rc;
+    if (const int rc = cost_to_go_cache(e, s, who, &p)) return rc;
     p.out = out;
     PGX_HIP(pgx::launch_cost_to_go(p, s));
     return PGX_OK;
@@ -1054,36 +1049,25 @@ int pgx_cost_to_go(pgx_env* e, int32_t flags, int32_t* out, void* stream) {
 // ---- cooperative planner (docs/SPEC.md S13) --------------------------------------------------------------
 int pgx_pibt_actions(pgx_env* e, int32_t flags, const int32_t* priority, void* actions, int32_t action_dtype,
                      int32_t* next_xy, void* stream) {
+    static const char who[] = "pgx_pibt_actions";
     // the argument checks come first and need no device
-    if (!actions) return fail_msg(PGX_E_INVALID, "pgx_pibt_actions: actions is null");
-    if (flags != 0) return fail_msg(PGX_E_INVALID, "pgx_pibt_actions: flags must be 0, got 0x%x", flags);
-    if (action_dtype < 0 || action_dtype > 2)
-        return fail_msg(PGX_E_INVALID, "pgx_pibt_actions: bad action_dtype %d", action_dtype);
-    const uintptr_t action_align = action_dtype == PGX_ACTION_I8 ? 0 : action_dtype == PGX_ACTION_I32 ? 3 : 7;
-    if (reinterpret_cast<uintptr_t>(actions) & action_align)
-        return fail_msg(PGX_E_INVALID, "pgx_pibt_actions: actions is not aligned to its element size");
-    if ((reinterpret_cast<uintptr_t>(priority) & 3) || (reinterpret_cast<uintptr_t>(next_xy) & 3))
-        return fail_msg(PGX_E_INVALID, "pgx_pibt_actions: priority and next_xy must be 4-byte aligned");
+    if (!actions) return fail_msg(PGX_E_INVALID, "%s: actions is null", who);
+    if (const int rc = check_flags(who, flags, 0)) return rc;
+    if (const int rc = check_action_dtype(who, action_dtype)) return rc;
+    static_assert(PGX_ACTION_I8 == 0 && PGX_ACTION_I32 == 1 && PGX_ACTION_I64 == 2, "action_bytes is indexed by the code");
+    static const size_t action_bytes[3] = {1, 4, 8};
+    if (const int rc = check_aligned(who, "actions", actions, action_bytes[action_dtype])) return rc;
+    if (const int rc = check_aligned(who, "priority", priority, 4)) return rc;
+    if (const int rc = check_aligned(who, "next_xy", next_xy, 4)) return rc;
     DeviceGuard guard;
-    if (const int rc = enter(guard, e, "pgx_pibt_actions", true)) return rc;
+    if (const int rc = enter(guard, e, who, true)) return rc;
     hipStream_t s = (hipStream_t)stream;
     pgx::CostToGoParams cp{};
-    pgx::CostToGoLayout l{};
-    if (const int rc = cost_to_go_cache(e, s, "pgx_pibt_actions", &cp, &l)) return rc;
+    if (const int rc = cost_to_go_cache(e, s, who, &cp)) return rc;
     PGX_HIP(pgx::launch_cost_to_go_refresh(cp, s));
-    pgx::PibtParams p{};
-    p.batch = cp.batch;
-    p.A = cp.A;
-    p.H = cp.H;
-    p.W = cp.W;
-    p.r = cp.r;
-    p.wpr = cp.wpr;
-    p.bmw = cp.bmw;
+    pgx::PibtParams p{cp};  // (the StateView base of cp; the planner's own fields follow)
     p.action_dtype = action_dtype;
-    p.cell_bytes = (int32_t)l.cell_bytes;
-    p.obst = cp.obst;
-    p.pos = cp.pos;
-    p.active = cp.active;
+    p.cell_bytes = cp.cell_bytes;
     p.field = cp.field;
     p.priority = priority;
     p.actions = actions;
@@ -1094,22 +1078,22 @@ int pgx_pibt_actions(pgx_env* e, int32_t flags, const int32_t* priority, void* a
 
 // ---- direction-to-goal planes (docs/SPEC.md S14) ----------------------------------------------------------
 int pgx_goal_directions(pgx_env* e, int32_t flags, void* out, int32_t format, void* stream) {
+    static const char who[] = "pgx_goal_directions";
     // the argument checks come first and need no device
-    if (!out) return fail_msg(PGX_E_INVALID, "pgx_goal_directions: out is null");
-    if (flags != 0) return fail_msg(PGX_E_INVALID, "pgx_goal_directions: flags must be 0, got 0x%x", flags);
+    if (!out) return fail_msg(PGX_E_INVALID, "%s: out is null", who);
+    if (const int rc = check_flags(who, flags, 0)) return rc;
     static_assert(PGX_DIRECTIONS_F32 == pgx::DIRECTIONS_F32 && PGX_DIRECTIONS_U8 == pgx::DIRECTIONS_U8 &&
                       PGX_DIRECTIONS_BITS == pgx::DIRECTIONS_BITS, "the kernels' format codes are the header's");
     if (format != PGX_DIRECTIONS_F32 && format != PGX_DIRECTIONS_U8 && format != PGX_DIRECTIONS_BITS)
-        return fail_msg(PGX_E_INVALID, "pgx_goal_directions: bad format %d", format);
-    if (format == PGX_DIRECTIONS_F32 && (reinterpret_cast<uintptr_t>(out) & 3))
-        return fail_msg(PGX_E_INVALID, "pgx_goal_directions: a float32 out must be 4-byte aligned");
+        return fail_msg(PGX_E_INVALID, "%s: bad format %d", who, format);
+    if (format == PGX_DIRECTIONS_F32)
+        if (const int rc = check_aligned(who, "a float32 out", out, 4)) return rc;
     DeviceGuard guard;
-    if (const int rc = enter(guard, e, "pgx_goal_directions", true)) return rc;
+    if (const int rc = enter(guard, e, who, true)) return rc;
     hipStream_t s = (hipStream_t)stream;
     pgx::CostToGoParams p{};
-    pgx::CostToGoLayout l{};
-    if (const int rc = cost_to_go_cache(e, s, "pgx_goal_directions", &p, &l)) return rc;
-    PGX_HIP(pgx::launch_goal_directions(p, l.cell_bytes, out, format, s));
+    if (const int rc = cost_to_go_cache(e, s, who, &p)) return rc;
+    PGX_HIP(pgx::launch_goal_directions(p, out, format, s));
     return PGX_OK;
 }
 
@@ -1125,23 +1109,17 @@ int64_t pgx_cost_to_go_builds(pgx_env* e, void* stream) {
 
 // ---- neighbour lists (docs/SPEC.md S12) -----------------------------------------------------------------
 int pgx_visible_agents(pgx_env* e, int32_t k, int32_t flags, int32_t* index, int8_t* offset, int32_t* count, void* stream) {
+    static const char who[] = "pgx_visible_agents";
     DeviceGuard guard;
-    if (const int rc = enter(guard, e, "pgx_visible_agents", true)) return rc;
-    if (k < 1 || k > PGX_MAX_NEIGHBOURS)
-        return fail_msg(PGX_E_INVALID, "pgx_visible_agents: k = %d is outside 1..%d", k, PGX_MAX_NEIGHBOURS);
-    if (flags != 0) return fail_msg(PGX_E_INVALID, "pgx_visible_agents: flags must be 0, got 0x%x", flags);
-    if (!index) return fail_msg(PGX_E_INVALID, "pgx_visible_agents: index is null");
-    if ((reinterpret_cast<uintptr_t>(index) & 3) || (reinterpret_cast<uintptr_t>(count) & 3) ||
-        (reinterpret_cast<uintptr_t>(offset) & 1))
-        return fail_msg(PGX_E_INVALID, "pgx_visible_agents: index and count must be 4-byte aligned, offset 2-byte aligned");
-    const pgx::StepParams sp = step_params(e, e->geo);
-    pgx::NeighbourParams p{};
-    p.batch = sp.batch;
-    p.A = sp.num_agents;
-    p.r = sp.r;
-    p.k = k;
-    p.pos = sp.pos;
-    p.active = sp.active;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    if (k < 1 || k > PGX_MAX_NEIGHBOURS) return fail_msg(PGX_E_INVALID, "%s: k = %d is outside 1..%d", who, k, PGX_MAX_NEIGHBOURS);
+    if (const int rc = check_flags(who, flags, 0)) return rc;
+    if (!index) return fail_msg(PGX_E_INVALID, "%s: index is null", who);
+    if (const int rc = check_aligned(who, "index", index, 4)) return rc;
+    if (const int rc = check_aligned(who, "count", count, 4)) return rc;
+    if (const int rc = check_aligned(who, "offset", offset, 2)) return rc;
+    const pgx::StateView v = state_view(e);
+    pgx::NeighbourParams p{v.batch, v.A, v.r, k, v.pos, v.active};
     p.index = index;
     p.offset = offset;
     p.count = count;

@@ -159,10 +159,10 @@ hipError_t dir_launch(const CostToGoParams& p, void* out, int format, hipStream_
 
 }  // namespace
 
-hipError_t launch_goal_directions(const CostToGoParams& p, size_t cell_bytes, void* out, int format, hipStream_t stream) {
+hipError_t launch_goal_directions(const CostToGoParams& p, void* out, int format, hipStream_t stream) {
     const hipError_t err = launch_cost_to_go_refresh(p, stream);
     if (err != hipSuccess) return err;
-    return cell_bytes == 4 ? dir_launch<uint32_t>(p, out, format, stream) : dir_launch<uint16_t>(p, out, format, stream);
+    return p.cell_bytes == 4 ? dir_launch<uint32_t>(p, out, format, stream) : dir_launch<uint16_t>(p, out, format, stream);
 }
 
 }  // namespace pgx

@@ -266,14 +266,25 @@ hipError_t launch_unpack_state(const uint32_t* pos, const uint32_t* tgt, const u
 hipError_t launch_occupancy(const uint32_t* pos, const uint8_t* active, uint8_t* occ, size_t n, int A, int PH,
                             int PW, hipStream_t stream);
 
+// ---- read-only queries on the engine state -----------------------------------------------------------------
+// The picture of the state a query kernel works on (pgx_api.cpp: state_view()); the argument blocks of the expert,
+// the cost-to-go cache and the planner start with it, the neighbour lists copy the four fields they read.
+struct StateView {
+    int32_t batch, A;        // environments, agents per environment
+    int32_t H, W;            // unpadded map size
+    int32_t r;               // observation radius = width of the padding ring
+    int32_t wpr;             // 32-bit words per padded bitmap row
+    int32_t bmw;             // words per env bitmap = (H + 2r) * wpr
+    const uint32_t* obst;    // [B][bmw] padded obstacle bitmaps, 1 bit per cell
+    const uint32_t* pos;     // [B][A] (x << 16) | y, padded coordinates
+    const uint32_t* tgt;     // [B][A]
+    const uint8_t* active;   // [B][A] ACTIVE_BIT | ACTIVE_GHOST
+};
+
 // ---- shortest-path expert (pgx_expert.hip) ------------------------------------------------------------
-struct ExpertParams {
-    int32_t batch, A, H, W, r, wpr, bmw;
+struct ExpertParams : StateView {
     int32_t with_agents;     // other active agents block their cells
     int32_t action_dtype;    // PGX_ACTION_*
-    const uint32_t* obst;    // [B][bmw] padded obstacle bitmaps
-    const uint32_t *pos, *tgt;
-    const uint8_t* active;
     uint32_t* occ;           // [B][H][ceil(W/32)] occupancy scratch of the large layout (expert_occupancy_words)
     void* actions;           // [B][A] of action_dtype
     int32_t* distance;       // [B][A], may be null
@@ -291,11 +302,8 @@ struct CostToGoLayout {
     size_t builds_off, field_off, tag_off, map_off, bytes;
 };
 CostToGoLayout cost_to_go_layout(int batch, int A, int H, int W);
-struct CostToGoParams {
-    int32_t batch, A, H, W, r, wpr, bmw;
-    const uint32_t* obst;    // [B][bmw] padded obstacle bitmaps
-    const uint32_t *pos, *tgt;
-    const uint8_t* active;
+struct CostToGoParams : StateView {
+    int32_t cell_bytes;      // of `field`: CostToGoLayout::cell_bytes
     uint32_t* map_bits;      // [B][H][ceil(W/32)] free bits the env's fields were built on
     uint32_t* tag;           // [B][A] packed padded target each field was built for; all ones: no field
     void* field;             // [B][A][H*W] distance to the tag's cell, u16 or u32 (cell_bytes); all ones: unreachable
@@ -311,15 +319,16 @@ hipError_t launch_cost_to_go(const CostToGoParams& p, hipStream_t stream);
 // ---- direction-to-goal planes (pgx_directions.hip) ---------------------------------------------------------
 enum { DIRECTIONS_F32 = 0, DIRECTIONS_U8 = 1, DIRECTIONS_BITS = 2 };  // PGX_DIRECTIONS_* (include/pogema_amd.h)
 // the refresh of the cost-to-go cache `p` describes (`p.out` is not used), then the planes of every agent into `out`:
-// [B][A][4][2r+1][2r+1] float32 or u8, or [B][A][2r+1][2r+1] u8 masks; cell_bytes: CostToGoLayout::cell_bytes
-hipError_t launch_goal_directions(const CostToGoParams& p, size_t cell_bytes, void* out, int format, hipStream_t stream);
+// [B][A][4][2r+1][2r+1] float32 or u8, or [B][A][2r+1][2r+1] u8 masks
+hipError_t launch_goal_directions(const CostToGoParams& p, void* out, int format, hipStream_t stream);
 
 // ---- neighbour lists (pgx_neighbours.hip) ---------------------------------------------------------------
+// (not derived from StateView: the kernel reads four of its fields, and this block of 56 bytes is fetched with two loads)
 struct NeighbourParams {
-    int32_t batch, A, r;
+    int32_t batch, A, r;     // as in StateView
     int32_t k;               // entries per agent, 1..PGX_MAX_NEIGHBOURS
-    const uint32_t* pos;     // [B][A] (x << 16) | y, padded coordinates
-    const uint8_t* active;   // [B][A]
+    const uint32_t* pos;     // as in StateView
+    const uint8_t* active;
     int32_t* index;          // [B][A][k]
     int8_t* offset;          // [B][A][k][2], 2-byte aligned, may be null
     int32_t* count;          // [B][A], may be null
@@ -327,13 +336,9 @@ struct NeighbourParams {
 hipError_t launch_visible_agents(const NeighbourParams& p, hipStream_t stream);
 
 // ---- cooperative planner (pgx_pibt.hip) ---------------------------------------------------------------------
-struct PibtParams {
-    int32_t batch, A, H, W, r, wpr, bmw;
+struct PibtParams : StateView {
     int32_t action_dtype;    // PGX_ACTION_*
     int32_t cell_bytes;      // of `field`: CostToGoLayout::cell_bytes
-    const uint32_t* obst;    // [B][bmw] padded obstacle bitmaps
-    const uint32_t* pos;     // [B][A]
-    const uint8_t* active;   // [B][A]
     const void* field;       // [B][A][H*W] the refreshed distance fields of the cost-to-go cache
     const int32_t* priority; // [B][A], null: every priority is 0
     void* actions;           // [B][A] of action_dtype

@@ -1,0 +1,170 @@
+"""VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
+cooperative planner and direction-to-goal planes.  Each is one C-ABI call into caller-owned or fresh output tensors;
+query_output() is the one place an `out` tensor is checked or allocated.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def query_output(name, out, dtypes, shape, device, align=None):
+    """The tensor a query writes its result `name` into: `out` itself when the caller gave one, else a fresh tensor of
+    dtypes[0].  `out` must be a contiguous tensor of one of `dtypes` (a dtype or a sequence of them) and of `shape` on
+    `device`, at an address that is a multiple of `align` bytes (default: its element size): anything else is a
+    ValueError that names `name` and what is expected.  Needs no engine and no GPU."""
+    dtypes = (dtypes,) if isinstance(dtypes, torch.dtype) else tuple(dtypes)
+    shape, device = tuple(shape), torch.device(device)
+    if out is None:
+        return torch.empty(shape, dtype=dtypes[0], device=device)
+    if not (isinstance(out, torch.Tensor) and out.dtype in dtypes and tuple(out.shape) == shape and out.is_contiguous()
+            and out.device == device and out.data_ptr() % (align or out.element_size()) == 0):
+        names = " / ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise ValueError(f"{name} must be a contiguous {names} tensor of shape {shape} on {device}, aligned to "
+                         f"{f'{align} bytes' if align else 'its element size'}")
+    return out
+
+
+def _split(out, names):
+    """The caller's `out` tuple as one entry per name; `out` = None: all to be allocated."""
+    if out is None:
+        return (None,) * len(names)
+    if len(out) != len(names):
+        raise ValueError(f"out must be ({', '.join(names)})")
+    for name, t in zip(names, out):
+        if t is None:  # (None would read as "allocate one": the caller gives every output or none)
+            raise ValueError(f"out[{name}] is None: out must be ({', '.join(names)}), every one a tensor")
+    return tuple(out)
+
+
+class QueryMixin:
+    """The queries of a VecPogema.  Expects of the class it is mixed into: `_handle`, `_lib`, `device`, `batch`,
+    `num_agents`, `window`, `_ACTION_CODE`, `_stream()`."""
+
+    def _action_dtypes(self, dtype, actions):
+        """The dtypes the `actions` output may have: the caller's tensor decides, else `dtype`."""
+        if actions is not None:
+            return tuple(self._ACTION_CODE)
+        if dtype not in self._ACTION_CODE:
+            raise ValueError(f"dtype must be one of torch.int8, torch.int32, torch.int64, got {dtype}")
+        return dtype
+
+    def expert_actions(self, agents_as_obstacles: bool = False, dtype=torch.int64, out=None):
+        """Shortest-path expert (docs/SPEC.md "Shortest-path expert"), computed on the device from the current state --
+        the state the next step() reads, which this call leaves untouched.  Returns (actions [batch, agents] of `dtype`,
+        distance int32 [batch, agents]): distance is the 4-connected BFS distance from each agent to its target over the
+        map's free cells (0 on the target, -1 without a path or for an inactive agent); the action is the lowest of
+        1..4 (up, down, left, right) that lowers it, 0 when the distance is <= 0.  `agents_as_obstacles=True`: the
+        cells of the other active agents are blocked too.  Stream-ordered, no host sync, capturable in a HIP graph.
+        `out=(actions, distance)`: caller-owned contiguous tensors on this device (actions int8 / int32 / int64)."""
+        B, A = self.batch, self.num_agents
+        actions, distance = _split(out, ("actions", "distance"))
+        actions = query_output("out[actions]", actions, self._action_dtypes(dtype, actions), (B, A), self.device)
+        distance = query_output("out[distance]", distance, torch.int32, (B, A), self.device)
+        _lib.check(self._lib.pgx_expert_actions(self._handle, 1 if agents_as_obstacles else 0, actions.data_ptr(),
+                                                self._ACTION_CODE[actions.dtype], distance.data_ptr(), self._stream()))
+        return actions, distance
+
+    def cost_to_go(self, out=None) -> torch.Tensor:
+        """Cost-to-go windows (docs/SPEC.md S11), computed on the device from the current state -- the state the next
+        step() reads, which this call leaves untouched.  Returns int32 [batch, agents, W, W] (W = 2 * obs_radius + 1, the
+        orientation of observation plane 0): the 4-connected BFS distance from each window cell to the agent's target
+        over the map's free cells; -1 outside the map, on obstacles, for unreachable cells and for every cell of an
+        inactive agent.  The centre equals expert_actions()' distance.  One distance field per agent is cached on the
+        device and rebuilt only when the agent's target cell or its env's map changed (cost_to_go_builds counts them).
+        The first call allocates that cache (pgx_cost_to_go_bytes) and must be made outside a graph capture; later calls
+        are stream-ordered, need no host sync and can be captured.  `out`: a caller-owned contiguous int32 tensor of
+        that shape on this device."""
+        shape = (self.batch, self.num_agents, self.window, self.window)
+        out = query_output("out", out, torch.int32, shape, self.device)
+        _lib.check(self._lib.pgx_cost_to_go(self._handle, 0, out.data_ptr(), self._stream()))
+        return out
+
+    @property
+    def cost_to_go_builds(self) -> int:
+        """Distance fields cost_to_go(), pibt_actions() and goal_directions() have built since this env was created
+        (synchronises the stream)."""
+        n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
+        if n < 0:
+            _lib.check(int(n))
+        return int(n)
+
+    def visible_agents(self, k: int = 13, out=None):
+        """Neighbour lists (docs/SPEC.md S12), computed on the device from the current state -- the state the next
+        step() reads, which this call leaves untouched.  Agent j is visible to agent i of the same env iff j != i, j is
+        active and |dx| <= obs_radius and |dy| <= obs_radius for (dx, dy) = xy_j - xy_i (the square observation window;
+        obstacles hide nobody, as in observation plane 1); an inactive agent sees nobody.  The visible agents are ordered
+        by (dx * dx + dy * dy, dx + r, dy + r, j): nearest first, ties in the window's row-major order, then by index.
+        Returns (index int32 [batch, agents, k]: the first min(count, k) of them, then -1;
+                 offset int8 [batch, agents, k, 2]: their (dx, dy), (0, 0) where index is -1;
+                 count int32 [batch, agents]: the number of visible agents, not capped by k).
+        `k` is 1..MAX_NEIGHBOURS (32).  One kernel launch: allocates nothing on the engine side, stream-ordered, no host
+        sync, capturable in a HIP graph from the first call.  `out=(index, offset, count)`: caller-owned contiguous
+        tensors of those dtypes and shapes on this device."""
+        B, A = self.batch, self.num_agents
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _lib.MAX_NEIGHBOURS:
+            raise ValueError(f"k must be an integer in 1..{_lib.MAX_NEIGHBOURS}, got {k!r}")
+        k = int(k)
+        index, offset, count = _split(out, ("index", "offset", "count"))
+        index = query_output("out[index]", index, torch.int32, (B, A, k), self.device)
+        offset = query_output("out[offset]", offset, torch.int8, (B, A, k, 2), self.device, align=2)
+        count = query_output("out[count]", count, torch.int32, (B, A), self.device)
+        _lib.check(self._lib.pgx_visible_agents(self._handle, k, 0, index.data_ptr(), offset.data_ptr(), count.data_ptr(),
+                                                self._stream()))
+        return index, offset, count
+
+    def pibt_actions(self, priority=None, dtype=torch.int64, out=None):
+        """Cooperative one-step planner (PIBT, docs/SPEC.md S13), computed on the device from the current state -- the
+        state the next step() reads, which this call leaves untouched.  Returns (actions [batch, agents] of `dtype`,
+        next_xy int32 [batch, agents, 2]: the cell each agent is sent to, unpadded (row, col)).  Every active agent gets
+        one of its own cell and its free neighbours, preferred by the distance to its target (cost_to_go()'s fields),
+        agents served by (-priority, index), with priority inheritance and backtracking: no two active agents get the
+        same cell and no two swap.  Inactive agents get action 0 and their own cell.  Under collision_system="soft"
+        step(actions) puts every active agent on its next_xy; under "priority" and "block_both" a move into a cell that
+        another agent leaves in the same step may be reverted.
+        `priority`: an integer tensor [batch, agents] on this device (converted to int32), None = all equal.
+        Shares cost_to_go()'s cache: whichever is called first allocates it (not inside a graph capture); later calls are
+        stream-ordered, need no host sync and can be captured.  `out=(actions, next_xy)`: caller-owned contiguous
+        tensors on this device (actions int8 / int32 / int64, next_xy int32)."""
+        B, A = self.batch, self.num_agents
+        if priority is not None:
+            if not isinstance(priority, torch.Tensor):
+                raise TypeError(f"priority must be a torch.Tensor or None, got {type(priority).__name__}")
+            if priority.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
+                raise TypeError(f"priority must be an integer tensor, got {priority.dtype}")
+            if tuple(priority.shape) != (B, A) or priority.device != self.device:
+                raise ValueError(f"priority must have shape {(B, A)} on {self.device}")
+            priority = priority.to(torch.int32).contiguous()
+        actions, next_xy = _split(out, ("actions", "next_xy"))
+        actions = query_output("out[actions]", actions, self._action_dtypes(dtype, actions), (B, A), self.device)
+        next_xy = query_output("out[next_xy]", next_xy, torch.int32, (B, A, 2), self.device)
+        _lib.check(self._lib.pgx_pibt_actions(self._handle, 0, priority.data_ptr() if priority is not None else None,
+                                              actions.data_ptr(), self._ACTION_CODE[actions.dtype], next_xy.data_ptr(),
+                                              self._stream()))
+        return actions, next_xy
+
+    def goal_directions(self, format: str = "float32", out=None) -> torch.Tensor:
+        """Direction-to-goal planes (docs/SPEC.md S14), the "heuristic channels" of DHC-style policies, computed on the
+        device from the current state -- the state the next step() reads, which this call leaves untouched.  Plane
+        a - 1 of an agent's window (W = 2 * obs_radius + 1, the orientation of observation plane 0) is 1 at a cell iff
+        move a (1..4: up, down, left, right) from that cell leads to a cell strictly closer to the agent's target; the
+        cell moved to is looked up in the agent's whole distance field, so the window's edge is exact.  All four are 0
+        on the target, wherever cost_to_go() gives -1 and for inactive agents.  The lowest plane set at the centre is
+        expert_actions()' action.
+        `format`: "float32" -> float32 [batch, agents, 4, W, W] of 0.0 / 1.0, ready for torch.cat behind the observation;
+                  "uint8"   -> uint8 [batch, agents, 4, W, W] of 0 / 1;
+                  "bits"    -> uint8 [batch, agents, W, W], bit a - 1 = plane a - 1.
+        Shares cost_to_go()'s cache: whichever of cost_to_go(), pibt_actions() and this is called first allocates it
+        (not inside a graph capture); later calls are stream-ordered, need no host sync and can be captured.  `out`: a
+        caller-owned contiguous tensor of that dtype and shape on this device."""
+        if format not in _lib.DIRECTIONS_FORMATS:
+            raise ValueError(f"format must be one of {sorted(_lib.DIRECTIONS_FORMATS)}, got {format!r}")
+        dtype = torch.float32 if format == "float32" else torch.uint8
+        planes = () if format == "bits" else (4,)
+        shape = (self.batch, self.num_agents) + planes + (self.window, self.window)
+        out = query_output("out", out, dtype, shape, self.device)
+        _lib.check(self._lib.pgx_goal_directions(self._handle, 0, out.data_ptr(), _lib.DIRECTIONS_FORMATS[format],
+                                                 self._stream()))
+        return out

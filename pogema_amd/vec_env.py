@@ -19,6 +19,7 @@ import torch
 from . import _lib
 from .grid_config import GridConfig
 from .placement import PlacementMixin, choose_buffers  # noqa: F401  (choose_buffers: re-exported)
+from .queries import QueryMixin
 from .semantics import Semantics
 
 
@@ -66,7 +67,7 @@ def parse_map_pool(maps) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(np.stack(out)))
 
 
-class VecPogema(PlacementMixin):
+class VecPogema(PlacementMixin, QueryMixin):
     """`batch` independent POGEMA environments on one MI355X.
 
     obs        float32 [batch, agents, 3, 2r+1, 2r+1]   (obstacles, agents, target)
@@ -827,168 +828,6 @@ class VecPogema(PlacementMixin):
                 raise ValueError("mask must have batch x agents entries")
         _lib.check(self._lib.pgx_set_targets(self._handle, t.data_ptr(), m.data_ptr() if m is not None else None,
                                              self._stream()))
-
-    def expert_actions(self, agents_as_obstacles: bool = False, dtype=torch.int64, out=None):
-        """Shortest-path expert (docs/SPEC.md "Shortest-path expert"), computed on the device from the current state --
-        the state the next step() reads, which this call leaves untouched.  Returns (actions [batch, agents] of `dtype`,
-        distance int32 [batch, agents]): distance is the 4-connected BFS distance from each agent to its target over the
-        map's free cells (0 on the target, -1 without a path or for an inactive agent); the action is the lowest of
-        1..4 (up, down, left, right) that lowers it, 0 when the distance is <= 0.  `agents_as_obstacles=True`: the
-        cells of the other active agents are blocked too.  Stream-ordered, no host sync, capturable in a HIP graph.
-        `out=(actions, distance)`: caller-owned contiguous tensors on this device (actions int8 / int32 / int64)."""
-        B, A = self.batch, self.num_agents
-        if out is not None:
-            if len(out) != 2:
-                raise ValueError("out must be (actions, distance)")
-            actions, distance = out
-            if (actions.dtype not in self._ACTION_CODE or tuple(actions.shape) != (B, A) or not actions.is_contiguous()
-                    or actions.device != self.device):
-                raise ValueError(f"out[actions] must be a contiguous int8 / int32 / int64 tensor of shape {(B, A)} on "
-                                 f"{self.device}")
-            if (distance.dtype != torch.int32 or tuple(distance.shape) != (B, A) or not distance.is_contiguous()
-                    or distance.device != self.device):
-                raise ValueError(f"out[distance] must be a contiguous int32 tensor of shape {(B, A)} on {self.device}")
-        else:
-            if dtype not in self._ACTION_CODE:
-                raise ValueError(f"dtype must be one of torch.int8, torch.int32, torch.int64, got {dtype}")
-            actions = torch.empty((B, A), dtype=dtype, device=self.device)
-            distance = torch.empty((B, A), dtype=torch.int32, device=self.device)
-        _lib.check(self._lib.pgx_expert_actions(self._handle, 1 if agents_as_obstacles else 0, actions.data_ptr(),
-                                                self._ACTION_CODE[actions.dtype], distance.data_ptr(), self._stream()))
-        return actions, distance
-
-    def cost_to_go(self, out=None) -> torch.Tensor:
-        """Cost-to-go windows (docs/SPEC.md S11), computed on the device from the current state -- the state the next
-        step() reads, which this call leaves untouched.  Returns int32 [batch, agents, W, W] (W = 2 * obs_radius + 1, the
-        orientation of observation plane 0): the 4-connected BFS distance from each window cell to the agent's target
-        over the map's free cells; -1 outside the map, on obstacles, for unreachable cells and for every cell of an
-        inactive agent.  The centre equals expert_actions()' distance.  One distance field per agent is cached on the
-        device and rebuilt only when the agent's target cell or its env's map changed (cost_to_go_builds counts them).
-        The first call allocates that cache (pgx_cost_to_go_bytes) and must be made outside a graph capture; later calls
-        are stream-ordered, need no host sync and can be captured.  `out`: a caller-owned contiguous int32 tensor of
-        that shape on this device."""
-        shape = (self.batch, self.num_agents, self.window, self.window)
-        if out is not None:
-            if (out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous()
-                    or out.device != self.device):
-                raise ValueError(f"out must be a contiguous int32 tensor of shape {shape} on {self.device}")
-        else:
-            out = torch.empty(shape, dtype=torch.int32, device=self.device)
-        _lib.check(self._lib.pgx_cost_to_go(self._handle, 0, out.data_ptr(), self._stream()))
-        return out
-
-    @property
-    def cost_to_go_builds(self) -> int:
-        """Distance fields cost_to_go(), pibt_actions() and goal_directions() have built since this env was created
-        (synchronises the stream)."""
-        n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
-        if n < 0:
-            _lib.check(int(n))
-        return int(n)
-
-    def visible_agents(self, k: int = 13, out=None):
-        """Neighbour lists (docs/SPEC.md S12), computed on the device from the current state -- the state the next
-        step() reads, which this call leaves untouched.  Agent j is visible to agent i of the same env iff j != i, j is
-        active and |dx| <= obs_radius and |dy| <= obs_radius for (dx, dy) = xy_j - xy_i (the square observation window;
-        obstacles hide nobody, as in observation plane 1); an inactive agent sees nobody.  The visible agents are ordered
-        by (dx * dx + dy * dy, dx + r, dy + r, j): nearest first, ties in the window's row-major order, then by index.
-        Returns (index int32 [batch, agents, k]: the first min(count, k) of them, then -1;
-                 offset int8 [batch, agents, k, 2]: their (dx, dy), (0, 0) where index is -1;
-                 count int32 [batch, agents]: the number of visible agents, not capped by k).
-        `k` is 1..MAX_NEIGHBOURS (32).  One kernel launch: allocates nothing on the engine side, stream-ordered, no host
-        sync, capturable in a HIP graph from the first call.  `out=(index, offset, count)`: caller-owned contiguous
-        tensors of those dtypes and shapes on this device."""
-        B, A = self.batch, self.num_agents
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _lib.MAX_NEIGHBOURS:
-            raise ValueError(f"k must be an integer in 1..{_lib.MAX_NEIGHBOURS}, got {k!r}")
-        k = int(k)
-        shapes = (("index", torch.int32, (B, A, k)), ("offset", torch.int8, (B, A, k, 2)), ("count", torch.int32, (B, A)))
-        if out is not None:
-            if len(out) != 3:
-                raise ValueError("out must be (index, offset, count)")
-            for t, (name, dtype, shape) in zip(out, shapes):
-                if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()
-                        or t.device != self.device or t.data_ptr() % t.element_size() or t.data_ptr() % 2):
-                    raise ValueError(f"out[{name}] must be a contiguous {dtype} tensor of shape {shape} on {self.device}"
-                                     + (" at an even address" if name == "offset" else ""))
-            index, offset, count = out
-        else:
-            index, offset, count = (torch.empty(shape, dtype=dtype, device=self.device) for _, dtype, shape in shapes)
-        _lib.check(self._lib.pgx_visible_agents(self._handle, k, 0, index.data_ptr(), offset.data_ptr(), count.data_ptr(),
-                                                self._stream()))
-        return index, offset, count
-
-    def pibt_actions(self, priority=None, dtype=torch.int64, out=None):
-        """Cooperative one-step planner (PIBT, docs/SPEC.md S13), computed on the device from the current state -- the
-        state the next step() reads, which this call leaves untouched.  Returns (actions [batch, agents] of `dtype`,
-        next_xy int32 [batch, agents, 2]: the cell each agent is sent to, unpadded (row, col)).  Every active agent gets
-        one of its own cell and its free neighbours, preferred by the distance to its target (cost_to_go()'s fields),
-        agents served by (-priority, index), with priority inheritance and backtracking: no two active agents get the
-        same cell and no two swap.  Inactive agents get action 0 and their own cell.  Under collision_system="soft"
-        step(actions) puts every active agent on its next_xy; under "priority" and "block_both" a move into a cell that
-        another agent leaves in the same step may be reverted.
-        `priority`: an integer tensor [batch, agents] on this device (converted to int32), None = all equal.
-        Shares cost_to_go()'s cache: whichever is called first allocates it (not inside a graph capture); later calls are
-        stream-ordered, need no host sync and can be captured.  `out=(actions, next_xy)`: caller-owned contiguous
-        tensors on this device (actions int8 / int32 / int64, next_xy int32)."""
-        B, A = self.batch, self.num_agents
-        if priority is not None:
-            if not isinstance(priority, torch.Tensor):
-                raise TypeError(f"priority must be a torch.Tensor or None, got {type(priority).__name__}")
-            if priority.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
-                raise TypeError(f"priority must be an integer tensor, got {priority.dtype}")
-            if tuple(priority.shape) != (B, A) or priority.device != self.device:
-                raise ValueError(f"priority must have shape {(B, A)} on {self.device}")
-            priority = priority.to(torch.int32).contiguous()
-        if out is not None:
-            if len(out) != 2:
-                raise ValueError("out must be (actions, next_xy)")
-            actions, next_xy = out
-            if (not isinstance(actions, torch.Tensor) or actions.dtype not in self._ACTION_CODE
-                    or tuple(actions.shape) != (B, A) or not actions.is_contiguous() or actions.device != self.device):
-                raise ValueError(f"out[actions] must be a contiguous int8 / int32 / int64 tensor of shape {(B, A)} on "
-                                 f"{self.device}")
-            if (not isinstance(next_xy, torch.Tensor) or next_xy.dtype != torch.int32 or tuple(next_xy.shape) != (B, A, 2)
-                    or not next_xy.is_contiguous() or next_xy.device != self.device):
-                raise ValueError(f"out[next_xy] must be a contiguous int32 tensor of shape {(B, A, 2)} on {self.device}")
-        else:
-            if dtype not in self._ACTION_CODE:
-                raise ValueError(f"dtype must be one of torch.int8, torch.int32, torch.int64, got {dtype}")
-            actions = torch.empty((B, A), dtype=dtype, device=self.device)
-            next_xy = torch.empty((B, A, 2), dtype=torch.int32, device=self.device)
-        _lib.check(self._lib.pgx_pibt_actions(self._handle, 0, priority.data_ptr() if priority is not None else None,
-                                              actions.data_ptr(), self._ACTION_CODE[actions.dtype], next_xy.data_ptr(),
-                                              self._stream()))
-        return actions, next_xy
-
-    def goal_directions(self, format: str = "float32", out=None) -> torch.Tensor:
-        """Direction-to-goal planes (docs/SPEC.md S14), the "heuristic channels" of DHC-style policies, computed on the
-        device from the current state -- the state the next step() reads, which this call leaves untouched.  Plane
-        a - 1 of an agent's window (W = 2 * obs_radius + 1, the orientation of observation plane 0) is 1 at a cell iff
-        move a (1..4: up, down, left, right) from that cell leads to a cell strictly closer to the agent's target; the
-        cell moved to is looked up in the agent's whole distance field, so the window's edge is exact.  All four are 0
-        on the target, wherever cost_to_go() gives -1 and for inactive agents.  The lowest plane set at the centre is
-        expert_actions()' action.
-        `format`: "float32" -> float32 [batch, agents, 4, W, W] of 0.0 / 1.0, ready for torch.cat behind the observation;
-                  "uint8"   -> uint8 [batch, agents, 4, W, W] of 0 / 1;
-                  "bits"    -> uint8 [batch, agents, W, W], bit a - 1 = plane a - 1.
-        Shares cost_to_go()'s cache: whichever of cost_to_go(), pibt_actions() and this is called first allocates it
-        (not inside a graph capture); later calls are stream-ordered, need no host sync and can be captured.  `out`: a
-        caller-owned contiguous tensor of that dtype and shape on this device."""
-        if format not in _lib.DIRECTIONS_FORMATS:
-            raise ValueError(f"format must be one of {sorted(_lib.DIRECTIONS_FORMATS)}, got {format!r}")
-        dtype = torch.float32 if format == "float32" else torch.uint8
-        planes = () if format == "bits" else (4,)
-        shape = (self.batch, self.num_agents) + planes + (self.window, self.window)
-        if out is not None:
-            if (not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape
-                    or not out.is_contiguous() or out.device != self.device):
-                raise ValueError(f"out must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
-        else:
-            out = torch.empty(shape, dtype=dtype, device=self.device)
-        _lib.check(self._lib.pgx_goal_directions(self._handle, 0, out.data_ptr(), _lib.DIRECTIONS_FORMATS[format],
-                                                 self._stream()))
-        return out
 
     def _wrap_obs(self, obs: torch.Tensor):
         """'default': the float32 tensor.  'POMAPF' / 'MAPF' (upstream `PogemaBase._pomapf_obs` / `_mapf_obs`):

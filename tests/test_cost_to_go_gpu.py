@@ -6,21 +6,9 @@ import numpy as np
 import pytest
 
 from cost_to_go_reference import cost_to_go_reference
+from util import installed_maps, lazy_torch, mixed_actions
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _maps(env):
-    torch = _torch()
-    from pogema_amd import _lib
-    maps = torch.empty((env.batch, env.height, env.width), dtype=torch.uint8, device=env.device)
-    _lib.check(env._lib.pgx_get_map(env._handle, maps.data_ptr(), env._stream()))
-    return maps.cpu().numpy()
 
 
 def _check(env, envs=None, what=""):
@@ -29,7 +17,7 @@ def _check(env, envs=None, what=""):
     st = env.get_state()
     active = st["is_active"].cpu().numpy()
     r = env.obs_radius
-    ref = cost_to_go_reference(_maps(env), st["agents_xy"].cpu().numpy(), st["targets_xy"].cpu().numpy(), active, r,
+    ref = cost_to_go_reference(installed_maps(env), st["agents_xy"].cpu().numpy(), st["targets_xy"].cpu().numpy(), active, r,
                                envs=envs)
     rows = slice(None) if envs is None else list(envs)
     bad = np.argwhere(got[rows] != ref[rows])
@@ -42,14 +30,6 @@ def _check(env, envs=None, what=""):
     return got
 
 
-def _mixed_actions(env, rng, p_expert=0.7):
-    torch = _torch()
-    a, _ = env.expert_actions()
-    rnd = torch.as_tensor(rng.integers(0, 5, size=(env.batch, env.num_agents)), device=env.device)
-    keep = torch.as_tensor(rng.random((env.batch, env.num_agents)) < p_expert, device=env.device)
-    return torch.where(keep, a, rnd)
-
-
 class CacheModel:
     """Host model of the cache contract: which fields a call must build."""
 
@@ -58,7 +38,7 @@ class CacheModel:
 
     def call(self, env):
         st = env.get_state()
-        maps = _maps(env)
+        maps = installed_maps(env)
         tgt = st["targets_xy"].cpu().numpy()
         active = st["is_active"].cpu().numpy()
         if self.maps is None:
@@ -91,7 +71,7 @@ def test_square_maps_match_reference(size, batch, agents):
     rng = np.random.default_rng(size)
     _check(env, what=f"size {size} reset")
     for _ in range(6):
-        env.step(_mixed_actions(env, rng))
+        env.step(mixed_actions(env, rng, p_expert=0.7))
     _check(env, what=f"size {size} after 6 steps")
     env.close()
 
@@ -105,7 +85,7 @@ def test_rectangular_and_large_maps(H, W, agents):
     env.reset(seed=6)
     _check(env, what=f"{H} x {W} reset")
     for _ in range(2):
-        env.step(_mixed_actions(env, rng))
+        env.step(mixed_actions(env, rng, p_expert=0.7))
     _check(env, what=f"{H} x {W} after steps")
     env.close()
 
@@ -119,7 +99,7 @@ def test_obs_radius(radius):
     rng = np.random.default_rng(radius)
     _check(env, what=f"radius {radius}")
     for _ in range(3):
-        env.step(_mixed_actions(env, rng))
+        env.step(mixed_actions(env, rng, p_expert=0.7))
     _check(env, what=f"radius {radius} after steps")
     env.close()
 
@@ -138,7 +118,7 @@ def test_modes_after_steps(collision, on_target):
         if t % 3 == 0:
             _check(env, what=f"{collision}/{on_target} step {t}")
             inactive_seen |= bool((~env.get_state()["is_active"]).any())
-        env.step(_mixed_actions(env, rng, p_expert=0.85))
+        env.step(mixed_actions(env, rng, p_expert=0.85))
     if on_target == "finish":
         assert inactive_seen, "no finished (hidden) agent was ever checked"
     env.close()
@@ -154,7 +134,7 @@ def test_empty_outside_false():
         rng = np.random.default_rng(2)
         for _ in range(2):
             _check(env, what=f"empty_outside=False size {size}")
-            env.step(_mixed_actions(env, rng))
+            env.step(mixed_actions(env, rng, p_expert=0.7))
         env.close()
 
 
@@ -204,7 +184,7 @@ def test_configs2_sample():
 
 
 def test_repeat_call_and_set_targets():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     for size in (16, 80):
         env = VecPogema(GridConfig(size=size, num_agents=8, obs_radius=3, density=0.3, seed=4), batch=6)
@@ -216,7 +196,7 @@ def test_repeat_call_and_set_targets():
         # move k active agents' targets to other free cells
         st = env.get_state()
         tgt = st["targets_xy"].cpu().numpy().copy()
-        maps = _maps(env)
+        maps = installed_maps(env)
         rng = np.random.default_rng(size)
         moved = [(0, 1), (2, 5), (5, 0), (5, 7)]
         for b, i in moved:
@@ -249,7 +229,7 @@ def test_reset_where_rebuilds_those_envs():
 
 @pytest.mark.parametrize("size", [12, 70])
 def test_restart_builds_exactly_the_changed_targets(size):
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     gc = GridConfig(size=size, num_agents=8, obs_radius=3, density=0.2, seed=9, on_target="restart",
                     max_episode_steps=10**6)
@@ -261,7 +241,7 @@ def test_restart_builds_exactly_the_changed_targets(size):
     total = 0
     for t in range(12):
         before = env.get_state()["targets_xy"].clone()
-        env.step(_mixed_actions(env, rng, p_expert=0.95))
+        env.step(mixed_actions(env, rng, p_expert=0.95))
         after = env.get_state()["targets_xy"]
         got, want = _call_and_count(env, model)
         assert got == want == int((before != after).any(-1).sum()), f"step {t}"
@@ -273,7 +253,7 @@ def test_restart_builds_exactly_the_changed_targets(size):
 
 @pytest.mark.parametrize("auto_reset", [True, "regenerate"])
 def test_auto_reset(auto_reset):
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     B, A = 12, 6
     gc = GridConfig(size=14, num_agents=A, obs_radius=3, density=0.3, seed=3, on_target="finish", max_episode_steps=6)
@@ -326,7 +306,7 @@ def test_map_pool():
 
 def test_state_untouched():
     """get_state() and the next step()'s outputs are identical with and without a preceding cost_to_go()."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     for size, coll, on_target in ((20, "soft", "restart"), (90, "block_both", "finish")):
         gc = GridConfig(size=size, num_agents=12, obs_radius=3, density=0.3, seed=31, collision_system=coll,
@@ -342,7 +322,7 @@ def test_state_untouched():
             sa, sb = a.get_state(occupancy=True), b.get_state(occupancy=True)
             for k in sa:
                 assert torch.equal(sa[k], sb[k]), f"size {size} step {t}: {k}"
-            assert np.array_equal(_maps(a), _maps(b))
+            assert np.array_equal(installed_maps(a), installed_maps(b))
             ra, rb = a.step(acts), b.step(acts)
             for x, y in zip(ra[:4], rb[:4]):
                 assert torch.equal(x, y), f"size {size} step {t}"
@@ -354,7 +334,7 @@ def test_state_untouched():
 def test_graph_replay_equals_eager(size):
     """cost_to_go() -> step() captured once after an eager call; replays (with lifelong rebuilds) equal a twin's eager
     run, windows and build count included."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     B, A = 16, 6
     gc = GridConfig(size=size, num_agents=A, obs_radius=3, density=0.3, seed=4, collision_system="soft",
@@ -394,7 +374,7 @@ def test_graph_replay_equals_eager(size):
 
 
 def test_first_call_inside_capture_is_refused():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     from pogema_amd._lib import PgxError
     env = VecPogema(GridConfig(size=70, num_agents=4, obs_radius=2, density=0.3, seed=12), batch=4)
@@ -413,7 +393,7 @@ def test_first_call_inside_capture_is_refused():
 
 
 def test_out_buffer_list_view_and_errors():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema, pogema_v0
     from pogema_amd._lib import PgxError
     env = VecPogema(GridConfig(size=16, num_agents=5, obs_radius=3, density=0.3, seed=21), batch=6)

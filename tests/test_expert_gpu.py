@@ -6,28 +6,16 @@ import numpy as np
 import pytest
 
 from expert_reference import expert_reference
+from util import installed_maps, lazy_torch, mixed_actions
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _maps(env):
-    torch = _torch()
-    from pogema_amd import _lib
-    maps = torch.empty((env.batch, env.height, env.width), dtype=torch.uint8, device=env.device)
-    _lib.check(env._lib.pgx_get_map(env._handle, maps.data_ptr(), env._stream()))
-    return maps.cpu().numpy()
 
 
 def _check(env, agents_as_obstacles, envs=None, what=""):
     """expert_actions() of every env (or of `envs`) == the reference on get_state() and the installed maps."""
     got_a, got_d = env.expert_actions(agents_as_obstacles=agents_as_obstacles)
     st = env.get_state()
-    ref_a, ref_d = expert_reference(_maps(env), st["agents_xy"].cpu().numpy(), st["targets_xy"].cpu().numpy(),
+    ref_a, ref_d = expert_reference(installed_maps(env), st["agents_xy"].cpu().numpy(), st["targets_xy"].cpu().numpy(),
                                     st["is_active"].cpu().numpy(), agents_as_obstacles, envs=envs)
     got_a, got_d = got_a.cpu().numpy(), got_d.cpu().numpy()
     rows = slice(None) if envs is None else list(envs)
@@ -36,15 +24,6 @@ def _check(env, agents_as_obstacles, envs=None, what=""):
                            f"distance {got_d[rows][tuple(bad[0])]} vs {ref_d[rows][tuple(bad[0])]}, "
                            f"action {got_a[rows][tuple(bad[0])]} vs {ref_a[rows][tuple(bad[0])]}")
     return got_d
-
-
-def _mixed_actions(env, rng, p_expert=0.7):
-    """Mostly the expert's actions (so that agents reach targets, finish and get new ones), some random."""
-    torch = _torch()
-    a, _ = env.expert_actions()
-    rnd = torch.as_tensor(rng.integers(0, 5, size=(env.batch, env.num_agents)), device=env.device)
-    keep = torch.as_tensor(rng.random((env.batch, env.num_agents)) < p_expert, device=env.device)
-    return torch.where(keep, a, rnd)
 
 
 @pytest.mark.parametrize("size,batch,agents", [(2, 8, 1), (8, 16, 6), (31, 8, 12), (32, 8, 16), (33, 6, 12), (63, 4, 16),
@@ -60,7 +39,7 @@ def test_square_maps_match_reference(size, batch, agents):
     for flag in (False, True):
         _check(env, flag, what=f"size {size} reset")
     for _ in range(6):
-        env.step(_mixed_actions(env, rng))
+        env.step(mixed_actions(env, rng, p_expert=0.7))
     for flag in (False, True):
         _check(env, flag, what=f"size {size} after 6 steps")
     env.close()
@@ -75,7 +54,7 @@ def test_1024_map_few_agents():
     for flag in (False, True):
         _check(env, flag, what="1024 reset")
     for _ in range(3):
-        env.step(_mixed_actions(env, rng))
+        env.step(mixed_actions(env, rng, p_expert=0.7))
     for flag in (False, True):
         _check(env, flag, what="1024 after 3 steps")
     env.close()
@@ -101,7 +80,7 @@ def test_map_strings_match_reference(name):
         if t % 4 == 0:
             for flag in (False, True):
                 _check(env, flag, what=f"{name} step {t}")
-        env.step(_mixed_actions(env, rng))
+        env.step(mixed_actions(env, rng, p_expert=0.7))
     env.close()
 
 
@@ -120,7 +99,7 @@ def test_modes_after_steps(collision, on_target):
             for flag in (False, True):
                 d = _check(env, flag, what=f"{collision}/{on_target} step {t}")
             inactive_seen |= bool((~env.get_state()["is_active"]).any())
-        env.step(_mixed_actions(env, rng, p_expert=0.85))
+        env.step(mixed_actions(env, rng, p_expert=0.85))
     if on_target == "finish":
         assert inactive_seen, "no finished (hidden) agent was ever checked"
     assert (d >= 0).any()
@@ -138,14 +117,14 @@ def test_empty_outside_false():
         for _ in range(2):
             for flag in (False, True):
                 _check(env, flag, what=f"empty_outside=False size {size}")
-            env.step(_mixed_actions(env, rng))
+            env.step(mixed_actions(env, rng, p_expert=0.7))
         env.close()
 
 
 def test_configs2_full_batch():
     """BASELINE configs[2]: 8192 envs of 64 x 64 with 64 agents.  Sampled envs against the reference; the whole batch
     against what any shortest path must satisfy (grid graphs are bipartite: d >= Manhattan distance, same parity)."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     gc = GridConfig(size=64, num_agents=64, obs_radius=5, density=0.3, seed=0)
     env = VecPogema(gc, batch=8192)
@@ -168,7 +147,7 @@ def test_configs2_full_batch():
 
 
 def test_dtypes_out_buffers_and_list_view():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema, pogema_v0
     gc = GridConfig(size=16, num_agents=5, obs_radius=3, density=0.3, seed=21)
     env = VecPogema(gc, batch=6)
@@ -190,6 +169,8 @@ def test_dtypes_out_buffers_and_list_view():
         env.expert_actions(out=(oa, torch.empty((6, 4), dtype=torch.int32, device=env.device)))
     with pytest.raises(ValueError):
         env.expert_actions(dtype=torch.float32)
+    with pytest.raises(ValueError):
+        env.expert_actions(out=(oa, None))
     env.close()
 
     one = pogema_v0(GridConfig(size=16, num_agents=5, obs_radius=3, density=0.3, seed=21))
@@ -230,7 +211,7 @@ def test_single_agent_follows_expert_to_its_target(size):
 
 def test_state_untouched():
     """get_state() and the next step()'s outputs are identical with and without a preceding expert_actions()."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     for size, coll in ((20, "soft"), (90, "block_both")):
         gc = GridConfig(size=size, num_agents=12, obs_radius=3, density=0.3, seed=31, collision_system=coll,
@@ -247,7 +228,7 @@ def test_state_untouched():
             sa, sb = a.get_state(occupancy=True), b.get_state(occupancy=True)
             for k in sa:
                 assert torch.equal(sa[k], sb[k]), f"size {size} step {t}: {k}"
-            assert np.array_equal(_maps(a), _maps(b))
+            assert np.array_equal(installed_maps(a), installed_maps(b))
             ra, rb = a.step(acts), b.step(acts)
             for x, y in zip(ra[:4], rb[:4]):
                 assert torch.equal(x, y), f"size {size} step {t}"
@@ -259,7 +240,7 @@ def test_state_untouched():
 @pytest.mark.parametrize("size", [16, 72])
 def test_expert_then_step_in_hip_graph(size):
     """expert_actions() -> step(those actions) captured once in a HIP graph; replays equal the eager run of a twin."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     B, A = 32, 8
     gc = GridConfig(size=size, num_agents=A, obs_radius=3, density=0.3, seed=4, collision_system="soft",
@@ -338,7 +319,7 @@ def test_more_searches_than_one_launch_grid():
 def test_first_flagged_call_on_a_large_map_is_refused_inside_capture():
     """The large layout's occupancy scratch is allocated by the first call with agents_as_obstacles; inside a graph
     capture that call is refused with a named error instead of allocating, and works eagerly afterwards."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     from pogema_amd._lib import PgxError
     env = VecPogema(GridConfig(size=70, num_agents=4, obs_radius=2, density=0.3, seed=12), batch=4)

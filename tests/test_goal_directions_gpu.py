@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from goal_directions_reference import goal_directions_reference, planes
+from util import installed_maps, lazy_torch, mixed_actions
 
 pytestmark = pytest.mark.gpu
 
@@ -19,28 +20,15 @@ FORMATS = ("float32", "uint8", "bits")
 MODES = (("priority", "finish"), ("block_both", "restart"), ("soft", "nothing"))
 
 
-def _torch():
-    import torch
-    return torch
-
-
-def _maps(env):
-    torch = _torch()
-    from pogema_amd import _lib
-    maps = torch.empty((env.batch, env.height, env.width), dtype=torch.uint8, device=env.device)
-    _lib.check(env._lib.pgx_get_map(env._handle, maps.data_ptr(), env._stream()))
-    return maps.cpu().numpy()
-
-
 def _reference(env, envs=None):
     st = env.get_state()
-    return goal_directions_reference(_maps(env), st["agents_xy"].cpu().numpy(), st["targets_xy"].cpu().numpy(),
+    return goal_directions_reference(installed_maps(env), st["agents_xy"].cpu().numpy(), st["targets_xy"].cpu().numpy(),
                                      st["is_active"].cpu().numpy(), env.obs_radius, envs=envs)
 
 
 def _check(env, what="", envs=None):
     """Every format of goal_directions() == the reference, bit for bit; returns the reference's masks."""
-    torch = _torch()
+    torch = lazy_torch()
     ref = _reference(env, envs)
     rows = slice(None) if envs is None else list(envs)
     w = env.window
@@ -60,14 +48,6 @@ def _check(env, what="", envs=None):
     return ref
 
 
-def _mixed_actions(env, rng, p_expert=0.7):
-    torch = _torch()
-    a, _ = env.expert_actions()
-    rnd = torch.as_tensor(rng.integers(0, 5, size=(env.batch, env.num_agents)), device=env.device)
-    keep = torch.as_tensor(rng.random((env.batch, env.num_agents)) < p_expert, device=env.device)
-    return torch.where(keep, a, rnd)
-
-
 def _reset_and_steps(gc, batch, seed, what, steps=4):
     from pogema_amd import VecPogema
     env = VecPogema(gc, batch=batch)
@@ -75,7 +55,7 @@ def _reset_and_steps(gc, batch, seed, what, steps=4):
     rng = np.random.default_rng(seed)
     _check(env, what=f"{what} reset")
     for _ in range(steps):
-        env.step(_mixed_actions(env, rng))
+        env.step(mixed_actions(env, rng, p_expert=0.7))
     _check(env, what=f"{what} after {steps} steps")
     env.close()
 
@@ -135,14 +115,14 @@ def test_modes_after_steps(collision, on_target):
             active = env.get_state()["is_active"].cpu().numpy()
             inactive_checked |= bool((~active).any())
             assert (ref[~active] == 0).all()
-        env.step(_mixed_actions(env, rng, p_expert=0.85))
+        env.step(mixed_actions(env, rng, p_expert=0.85))
     if on_target == "finish":
         assert inactive_checked, "no finished (hidden) agent was ever checked"
     env.close()
 
 
 def test_formats_agree():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     env = VecPogema(GridConfig(size=24, num_agents=13, obs_radius=4, density=0.3, seed=3), batch=5)
     env.reset(seed=3)
@@ -162,7 +142,7 @@ def test_formats_agree():
 def test_misaligned_out(fmt, agents, batch):
     """`out` one element past a 16-byte boundary, and the one-byte formats also four bytes past it: the same result as
     an aligned one, nothing written around it."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     env = VecPogema(GridConfig(size=16, num_agents=agents, obs_radius=3, density=0.3, seed=5), batch=batch)
     env.reset(seed=5)
@@ -197,16 +177,16 @@ def test_centre_cell_is_the_expert_action():
                 lowest[(centre >> (a - 1)) & 1 == 1] = a
             assert np.array_equal(lowest, actions)
             assert np.array_equal(centre == 0, dist <= 0)
-            env.step(_mixed_actions(env, rng, p_expert=0.9))
+            env.step(mixed_actions(env, rng, p_expert=0.9))
         env.close()
 
 
 def test_obstacle_target_gives_all_zero():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     env = VecPogema(GridConfig(size=16, num_agents=6, obs_radius=3, density=0.3, seed=9), batch=4)
     env.reset(seed=9)
-    maps = _maps(env)
+    maps = installed_maps(env)
     tgt = env.get_state()["targets_xy"].cpu().numpy().copy()
     hit = [(0, 2), (3, 5)]
     for b, i in hit:
@@ -221,7 +201,7 @@ def test_obstacle_target_gives_all_zero():
 
 
 def test_cache_contract():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     for size in (16, 80):
         B, A = 5, 6
@@ -241,7 +221,7 @@ def test_cache_contract():
         env.goal_directions()
         assert env.cost_to_go_builds == B * A
         tgt = env.get_state()["targets_xy"].cpu().numpy().copy()
-        maps = _maps(env)
+        maps = installed_maps(env)
         rng = np.random.default_rng(size)
         moved = [(0, 1), (2, 5), (4, 0)]
         for b, i in moved:
@@ -257,7 +237,7 @@ def test_cache_contract():
 
 
 def test_first_call_inside_capture_is_refused():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     from pogema_amd._lib import PgxError
     env = VecPogema(GridConfig(size=20, num_agents=4, obs_radius=2, density=0.3, seed=12), batch=4)
@@ -277,7 +257,7 @@ def test_first_call_inside_capture_is_refused():
 
 def test_state_untouched():
     """get_state() and the next step()'s outputs are identical with and without a preceding goal_directions()."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     for size, coll, on_target in ((20, "soft", "restart"), (70, "block_both", "finish")):
         gc = GridConfig(size=size, num_agents=13, obs_radius=3, density=0.3, seed=31, collision_system=coll,
@@ -294,7 +274,7 @@ def test_state_untouched():
             sa, sb = a.get_state(occupancy=True), b.get_state(occupancy=True)
             for k in sa:
                 assert torch.equal(sa[k], before[k]) and torch.equal(sa[k], sb[k]), f"size {size} step {t}: {k}"
-            assert np.array_equal(_maps(a), _maps(b))
+            assert np.array_equal(installed_maps(a), installed_maps(b))
             ra, rb = a.step(acts), b.step(acts)
             for x, y in zip(ra[:4], rb[:4]):
                 assert torch.equal(x, y), f"size {size} step {t}"
@@ -306,7 +286,7 @@ def test_state_untouched():
 def test_graph_replay_equals_eager(size):
     """goal_directions() captured once after an eager call; replays after further steps (and after new targets, which
     make fields stale) equal the eager result on the same state."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     B, A = 6, 6
     gc = GridConfig(size=size, num_agents=A, obs_radius=3, density=0.3, seed=4, collision_system="soft",
@@ -326,7 +306,7 @@ def test_graph_replay_equals_eager(size):
         for fmt in FORMATS:
             env.goal_directions(format=fmt, out=outs[fmt])
     built = env.cost_to_go_builds
-    maps = _maps(env)
+    maps = installed_maps(env)
     for t in range(8):
         a, _ = env.expert_actions()
         env.step(a)
@@ -361,14 +341,14 @@ def test_grid_stride_loop():
     env = VecPogema(GridConfig(size=6, num_agents=A, obs_radius=1, density=0.2, seed=2, max_episode_steps=64), batch=B)
     env.reset(seed=2)
     _check(env, what="grid-stride reset")
-    env.step(_mixed_actions(env, np.random.default_rng(2)))
+    env.step(mixed_actions(env, np.random.default_rng(2), p_expert=0.7))
     ref = _check(env, what="grid-stride after a step")
     assert ref[-1].any() or ref[-2].any()
     env.close()
 
 
 def test_out_buffer_list_view_and_errors():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema, pogema_v0
     from pogema_amd._lib import PgxError
     env = VecPogema(GridConfig(size=16, num_agents=5, obs_radius=3, density=0.3, seed=21), batch=6)

@@ -9,32 +9,20 @@ import pytest
 
 from pibt_reference import check_invariants, pibt_reference
 from test_visible_agents_gpu import LAYOUTS
+from util import installed_maps, lazy_torch, mixed_actions
 
 pytestmark = pytest.mark.gpu
 
 
-def _torch():
-    import torch
-    return torch
-
-
-def _maps(env):
-    torch = _torch()
-    from pogema_amd import _lib
-    maps = torch.empty((env.batch, env.height, env.width), dtype=torch.uint8, device=env.device)
-    _lib.check(env._lib.pgx_get_map(env._handle, maps.data_ptr(), env._stream()))
-    return maps.cpu().numpy()
-
-
 def _check(env, priority=None, what="", dtype=None, invariants=False):
     """pibt_actions(priority) == the reference on get_state() + the installed maps; returns (actions, next_xy) tensors."""
-    torch = _torch()
+    torch = lazy_torch()
     kw = {} if dtype is None else {"dtype": dtype}
     actions, next_xy = env.pibt_actions(priority=priority, **kw)
     assert actions.dtype == (torch.int64 if dtype is None else dtype) and tuple(actions.shape) == (env.batch, env.num_agents)
     assert next_xy.dtype == torch.int32 and tuple(next_xy.shape) == (env.batch, env.num_agents, 2)
     st = env.get_state()
-    maps = _maps(env)
+    maps = installed_maps(env)
     pos, active = st["agents_xy"].cpu().numpy(), st["is_active"].cpu().numpy()
     ref_a, ref_n = pibt_reference(maps, pos, st["targets_xy"].cpu().numpy(), active,
                                   None if priority is None else priority.cpu().numpy())
@@ -49,18 +37,10 @@ def _check(env, priority=None, what="", dtype=None, invariants=False):
 
 
 def _priorities(env, rng):
-    torch = _torch()
+    torch = lazy_torch()
     shape = (env.batch, env.num_agents)
     return (None, torch.as_tensor(rng.integers(-3, 4, size=shape), dtype=torch.int32, device=env.device),
             torch.full(shape, 7, dtype=torch.int32, device=env.device))
-
-
-def _mixed_actions(env, rng, p_expert=0.8):
-    torch = _torch()
-    a, _ = env.expert_actions()
-    rnd = torch.as_tensor(rng.integers(0, 5, size=(env.batch, env.num_agents)), device=env.device)
-    keep = torch.as_tensor(rng.random((env.batch, env.num_agents)) < p_expert, device=env.device)
-    return torch.where(keep, a, rnd)
 
 
 @pytest.mark.parametrize("agents,size,batch", LAYOUTS)
@@ -77,7 +57,7 @@ def test_every_lane_layout_matches_reference(agents, size, batch):
         for k, prio in enumerate(prios if agents < 1024 else prios[1:2]):
             _check(env, prio, what=f"A={agents} r={r} reset prio#{k}", invariants=True)
         for _ in range(4):
-            env.step(_mixed_actions(env, rng))
+            env.step(mixed_actions(env, rng, p_expert=0.8))
         for k, prio in enumerate(prios[:2] if agents < 1024 else prios[:1]):
             _check(env, prio, what=f"A={agents} r={r} after 4 steps prio#{k}")
         env.close()
@@ -95,7 +75,7 @@ def test_non_square_maps(name, rows, cols):
     prios = _priorities(env, rng)
     for t in range(5):
         _check(env, prios[t % 3], what=f"{name} step {t}", invariants=t == 0)
-        env.step(_mixed_actions(env, rng))
+        env.step(mixed_actions(env, rng, p_expert=0.8))
     env.close()
 
 
@@ -135,7 +115,7 @@ def test_crowded_agents_side_by_side_on_a_large_map():
 
 
 def test_every_action_dtype():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     env = VecPogema(GridConfig(size=10, num_agents=14, obs_radius=3, density=0.2, seed=9, collision_system="soft"), batch=9)
     env.reset(seed=9)
@@ -173,7 +153,7 @@ def test_modes_after_steps(collision, on_target):
             _check(env, prios[(t // 3) % 3], what=f"{collision}/{on_target} step {t}")
             inactive_seen |= bool((~st["is_active"]).any())
         # mostly the planner itself, some noise so that agents also stand on one cell under `soft`
-        a = env.pibt_actions(priority=prios[1])[0] if t % 2 else _mixed_actions(env, rng, p_expert=0.85)
+        a = env.pibt_actions(priority=prios[1])[0] if t % 2 else mixed_actions(env, rng, p_expert=0.85)
         env.step(a)
     if on_target == "finish":
         assert inactive_seen, "no finished (hidden) agent was ever checked"
@@ -183,7 +163,7 @@ def test_modes_after_steps(collision, on_target):
 
 
 def test_map_pool_and_set_targets():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     rng = np.random.default_rng(77)
     H = W = 14
@@ -200,7 +180,7 @@ def test_map_pool_and_set_targets():
     env.reset(seed=3)                      # other maps under the same cache
     _check(env, prios[1], what="pool second reset")
     # new targets: free cells of each env's own map (its first free cells, one per agent)
-    maps = _maps(env)
+    maps = installed_maps(env)
     t = np.stack([np.argwhere(m == 0)[rng.permutation(int((m == 0).sum()))[:6]] for m in maps]).astype(np.int32)
     env.set_targets(t)
     assert np.array_equal(env.get_state()["targets_xy"].cpu().numpy(), t)
@@ -209,7 +189,7 @@ def test_map_pool_and_set_targets():
 
 
 def test_soft_step_puts_every_planned_agent_on_its_next_cell():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, PibtPolicy, VecPogema
     gc = GridConfig(size=10, num_agents=24, obs_radius=3, density=0.2, seed=17, collision_system="soft",
                     on_target="finish", max_episode_steps=64)
@@ -258,7 +238,7 @@ def test_head_on_corridor_is_solved_where_the_expert_deadlocks():
     the corridor or in the bay, at most L steps from its target (the corridor's far end is L - 1 away, the bay
     c + 1 <= L - 1).  From then on it is alone and every step brings it one cell closer: at most L more steps.
     Bound: (L - 1) + L = 2 L - 1 = 17 steps.  (The reference takes 13 on this instance.)"""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, PibtPolicy, VecPogema
     L = 9
     grid = "#" * L + "\n" + "######.##" + "\n" + "." * L
@@ -315,7 +295,7 @@ def test_cache_is_shared_with_cost_to_go():
 def test_state_untouched():
     """save_state() blobs before and after the call are equal, and the next step() equals that of a twin env that never
     planned."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     gc = GridConfig(size=14, num_agents=12, obs_radius=3, density=0.2, seed=31, collision_system="soft",
                     on_target="restart", max_episode_steps=32)
@@ -339,7 +319,7 @@ def test_state_untouched():
 
 
 def test_first_call_inside_a_capture_is_refused_and_a_later_capture_replays():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     from pogema_amd._lib import PgxError
     B, A = 16, 10
@@ -367,7 +347,7 @@ def test_first_call_inside_a_capture_is_refused_and_a_later_capture_replays():
         env.pibt_actions(priority=prio, out=out)
     rng = np.random.default_rng(4)
     for t in range(12):
-        env.step(out[0].clone() if t % 2 else _mixed_actions(env, rng))   # the state changes, targets are redrawn
+        env.step(out[0].clone() if t % 2 else mixed_actions(env, rng, p_expert=0.8))   # the state changes, targets are redrawn
         prio.copy_(torch.as_tensor(rng.integers(-2, 3, size=(B, A)), dtype=torch.int32))
         g.replay()
         got_a, got_n = out[0].clone(), out[1].clone()
@@ -377,7 +357,7 @@ def test_first_call_inside_a_capture_is_refused_and_a_later_capture_replays():
 
 
 def test_out_tensors_refused_arguments_and_list_view():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema, pogema_v0
     from pogema_amd._lib import PgxError
     B, A = 6, 9
@@ -399,6 +379,7 @@ def test_out_tensors_refused_arguments_and_list_view():
         (torch.empty((B, 2 * A), dtype=torch.int32, device=env.device)[:, ::2], on),
         (torch.empty((B, A), dtype=torch.int32), on),
         (oa,),
+        (oa, None),
     ]
     for out in bad_out:
         with pytest.raises(ValueError, match="out"):

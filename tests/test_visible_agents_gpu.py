@@ -6,13 +6,9 @@ import numpy as np
 import pytest
 
 from visible_agents_reference import visible_agents_reference
+from util import lazy_torch, mixed_actions
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def _reference(env, k):
@@ -32,15 +28,6 @@ def _check(env, k, what="", full=None):
         assert bad.size == 0, (f"{what} k={k}: {len(bad)} mismatches in {name}, first at {bad[0].tolist()}: "
                                f"{g[tuple(bad[0])]} vs {w[tuple(bad[0])]}")
     return ref
-
-
-def _mixed_actions(env, rng, p_expert=0.8):
-    """Mostly the expert's actions (so that agents reach targets, finish and get new ones), some random."""
-    torch = _torch()
-    a, _ = env.expert_actions()
-    rnd = torch.as_tensor(rng.integers(0, 5, size=(env.batch, env.num_agents)), device=env.device)
-    keep = torch.as_tensor(rng.random((env.batch, env.num_agents)) < p_expert, device=env.device)
-    return torch.where(keep, a, rnd)
 
 
 KS = (1, 5, 8, 13, 16, 17, 32)
@@ -65,7 +52,7 @@ def test_every_lane_layout_matches_reference(agents, size, batch):
         for k in KS:
             _check(env, k, what=f"A={agents} r={r} reset", full=full)
         for _ in range(4):
-            env.step(_mixed_actions(env, rng))
+            env.step(mixed_actions(env, rng, p_expert=0.8))
         full = _reference(env, max(KS))
         for k in KS:
             _check(env, k, what=f"A={agents} r={r} after 4 steps", full=full)
@@ -85,7 +72,7 @@ def test_non_square_maps(name, rows, cols):
             if t % 2 == 0:
                 for k in KS:
                     _check(env, k, what=f"{name} r={r} step {t}")
-            env.step(_mixed_actions(env, rng))
+            env.step(mixed_actions(env, rng, p_expert=0.8))
         env.close()
 
 
@@ -98,12 +85,12 @@ def test_1024_map():
     for k in (1, 13, 32):
         _check(env, k, what="1024 reset")
     for _ in range(3):
-        env.step(_mixed_actions(env, rng))
+        env.step(mixed_actions(env, rng, p_expert=0.8))
     for k in (1, 13, 32):
         _check(env, k, what="1024 after 3 steps")
     env.close()
     # the same map size with the agents placed next to each other at the far corner (coordinates above 1000)
-    torch = _torch()
+    torch = lazy_torch()
     obst = np.zeros((1, 1024, 1024), dtype=np.uint8)
     cells = np.array([(1023 - i // 6, 1023 - i % 6) for i in range(30)], dtype=np.int32)[None]
     targets = np.array([(i // 6, i % 6) for i in range(30)], dtype=np.int32)[None]
@@ -135,7 +122,7 @@ def test_modes_after_steps(collision, on_target):
                 ref = _check(env, k, what=f"{collision}/{on_target} step {t}")
             seen = max(seen, int(ref[2].max()))
             inactive_seen |= bool((~env.get_state()["is_active"]).any())
-        env.step(_mixed_actions(env, rng, p_expert=0.85))
+        env.step(mixed_actions(env, rng, p_expert=0.85))
     if on_target == "finish":
         assert inactive_seen, "no finished (hidden) agent was ever checked"
     assert seen > 0
@@ -154,7 +141,7 @@ def test_crowded_map_truncates_the_lists():
     _check(env, K, what="crowded")
     rng = np.random.default_rng(2)
     for _ in range(3):
-        env.step(_mixed_actions(env, rng))
+        env.step(mixed_actions(env, rng, p_expert=0.8))
     ref = _check(env, K, what="crowded after 3 steps")
     assert ref[2].max() > K
     env.close()
@@ -164,7 +151,7 @@ def test_crowded_map_truncates_the_lists():
 @pytest.mark.parametrize("size,agents,r", [(16, 8, 5), (32, 16, 5), (64, 64, 5)])
 def test_lists_rebuild_plane_one_of_the_observation(collision, soft_occupancy, size, agents, r):
     """Ones scattered at (r + dx, r + dy) for an active agent's list, plus its own centre, are plane 1 of observe()."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, Semantics, VecPogema
     K = 32
     gc = GridConfig(size=size, num_agents=agents, obs_radius=r, density=0.3, seed=13, collision_system=collision,
@@ -186,12 +173,12 @@ def test_lists_rebuild_plane_one_of_the_observation(collision, soft_occupancy, s
         built = built.view(16, agents, W, W)
         assert active.any()
         assert torch.equal(built[active], plane[active].to(torch.float32)), f"{collision} step {t}"
-        env.step(_mixed_actions(env, rng))
+        env.step(mixed_actions(env, rng, p_expert=0.8))
     env.close()
 
 
 def test_out_tensors_and_refused_arguments():
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     B, A, K = 6, 9, 5
     env = VecPogema(GridConfig(size=10, num_agents=A, obs_radius=3, density=0.1, seed=21), batch=B)
@@ -218,6 +205,7 @@ def test_out_tensors_and_refused_arguments():
         (torch.empty((B, A, 2 * K), dtype=torch.int32, device=env.device)[:, :, ::2], oo, oc),  # contiguity
         (torch.empty((B, A, K), dtype=torch.int32), oo, oc),                              # device
         (oi, oo),
+        (oi, None, oc),                                                                   # an entry left out
     ]
     for out in bad:
         with pytest.raises(ValueError):
@@ -230,7 +218,7 @@ def test_out_tensors_and_refused_arguments():
 
 def test_optional_outputs_through_the_c_abi():
     """offset = NULL / count = NULL: the other outputs are as usual and nothing else is written."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema, _lib
     B, A, K = 5, 20, 7
     env = VecPogema(GridConfig(size=9, num_agents=A, obs_radius=4, density=0.0, seed=8), batch=B)
@@ -278,7 +266,7 @@ def test_before_reset_is_refused():
 def test_state_untouched():
     """save_state() blobs before and after the call are equal, and the next step() equals that of a twin env that never
     called it."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     gc = GridConfig(size=14, num_agents=12, obs_radius=3, density=0.2, seed=31, collision_system="soft",
                     on_target="restart", max_episode_steps=32)
@@ -304,7 +292,7 @@ def test_state_untouched():
 def test_visible_agents_then_step_in_hip_graph():
     """visible_agents(out=...) -> step() captured once in a HIP graph; 30 replays equal the eager run of a twin and the
     reference.  No call outside the capture is needed beforehand (the warm-up is torch's recipe, not the engine's)."""
-    torch = _torch()
+    torch = lazy_torch()
     from pogema_amd import GridConfig, VecPogema
     B, A, K = 32, 12, 13
     gc = GridConfig(size=12, num_agents=A, obs_radius=3, density=0.2, seed=4, collision_system="soft",
@@ -329,7 +317,7 @@ def test_visible_agents_then_step_in_hip_graph():
         graphed.visible_agents(k=K, out=out_v)
         out = graphed.step(acts)
     for t in range(30):
-        acts.copy_(_mixed_actions(eager, rng))
+        acts.copy_(mixed_actions(eager, rng, p_expert=0.8))
         want = _check(eager, K, what=f"eager step {t}")
         g.replay()
         ref = eager.step(acts)

@@ -306,3 +306,28 @@ def odd_cases(seed, n):
         what = f"odd case {done}: {H}x{W}, {A} agents, {kw}, starts {starts.tolist()}, targets {targets.tolist()}"
         yield what, (obst[None], starts[None].astype(np.int32), targets[None].astype(np.int32), actions), kw
         done += 1
+
+
+# ---- shared by the GPU suites of the state queries ----
+def lazy_torch():
+    """torch, imported on first use (collecting a GPU test module must not need it)."""
+    import torch
+    return torch
+
+
+def installed_maps(env):
+    """The maps a VecPogema runs, uint8 [batch, H, W] on the host (pgx_get_map)."""
+    torch = lazy_torch()
+    from pogema_amd import _lib
+    maps = torch.empty((env.batch, env.height, env.width), dtype=torch.uint8, device=env.device)
+    _lib.check(env._lib.pgx_get_map(env._handle, maps.data_ptr(), env._stream()))
+    return maps.cpu().numpy()
+
+
+def mixed_actions(env, rng, p_expert):
+    """Mostly the expert's actions (so that agents reach targets, finish and get new ones), some random."""
+    torch = lazy_torch()
+    a, _ = env.expert_actions()
+    rnd = torch.as_tensor(rng.integers(0, 5, size=(env.batch, env.num_agents)), device=env.device)
+    keep = torch.as_tensor(rng.random((env.batch, env.num_agents)) < p_expert, device=env.device)
+    return torch.where(keep, a, rnd)
