@@ -379,8 +379,8 @@ int pgx_cost_to_go(pgx_env* env, int32_t flags, int32_t* out, void* stream);
  * rounded up to a multiple of 16 + 4 * B * A (target tags) + 4 * B * H * ceil(W / 32) (map copies).  Returns the status
  * code of pgx_check_config for a configuration it refuses. */
 int64_t pgx_cost_to_go_bytes(const pgx_config* cfg);
-/* Distance fields pgx_cost_to_go, pgx_pibt_actions and pgx_goal_directions have built since the handle was created (0
- * before the first call of any of them).  Synchronises `stream`. */
+/* Distance fields pgx_cost_to_go, pgx_pibt_actions, pgx_goal_directions and pgx_shield_actions have built since the
+ * handle was created (0 before the first call of any of them).  Synchronises `stream`. */
 int64_t pgx_cost_to_go_builds(pgx_env* env, void* stream);
 
 /* Neighbour lists (docs/SPEC.md S12), read from the current device state -- the state the next pgx_step reads, which
@@ -427,6 +427,36 @@ int pgx_visible_agents(pgx_env* env, int32_t k, int32_t flags, int32_t* index, i
  * reset, like pgx_step. */
 int pgx_pibt_actions(pgx_env* env, int32_t flags, const int32_t* priority, void* actions, int32_t action_dtype,
                      int32_t* next_xy, void* stream);
+
+/* Collision shielding (docs/SPEC.md S15): pgx_pibt_actions' planner -- the same planned agents, serving order
+ * (-priority, index), priority inheritance, backtracking, outputs and guarantees -- with every agent's candidate cells
+ * ordered by the caller's action scores instead of by the distance to its target.  Among the agent's own cell and its
+ * four neighbours that lie inside the map and are free of obstacles (the others are dropped whatever their score: the
+ * call is also the action mask), the higher score comes first, then the lower action; -0.0 equals +0.0, +inf and -inf
+ * are ordinary values and a NaN ranks below -inf.  Every planned agent gets the best-scored action that is jointly
+ * collision-free, for any scores.  The call is deterministic: to sample, add Gumbel noise to the logits first.
+ *   flags       0, or PGX_SHIELD_TIE_DISTANCE: equal scores are ordered as pgx_pibt_actions orders its candidates
+ *               (distance to the target, unoccupied first) before the action; with all five scores of every agent
+ *               equal the result is pgx_pibt_actions' bit for bit
+ *   scores      device [batch, agents, 5] of score_dtype (PGX_SCORES_*), contiguous, aligned to its element size;
+ *               entry a is the score of action a.  Must not be NULL.
+ *   priority    device i32 [batch, agents]; NULL: every priority is 0 (index order)
+ *   actions     device [batch, agents] of action_dtype (PGX_ACTION_*).  Must not be NULL.
+ *   next_xy     device i32 [batch, agents, 2]: the next cells, unpadded (row, col).  May be NULL.
+ *   overridden  device u8 [batch, agents]: 1 iff the agent is planned and its action is not the argmax of its five
+ *               scores (ties to the lowest action, NaN lowest), else 0.  May be NULL.
+ * Without PGX_SHIELD_TIE_DISTANCE: one kernel launch that reads no distance field; allocates nothing (the first call
+ * included), asynchronous on `stream`, no host sync, capturable in a HIP graph from the first call.  With it the call
+ * shares pgx_cost_to_go's distance-field cache under pgx_pibt_actions' rules: it refreshes the cache, and whichever entry
+ * point that uses the cache is called first allocates it -- inside a graph capture that first call returns PGX_E_STATE.
+ * PGX_E_INVALID for a NULL `scores` or `actions`, unknown flag bits, a bad score_dtype or action_dtype or a misaligned
+ * pointer (checked before the handle: no device needed); PGX_E_STATE before the first reset, like pgx_step. */
+#define PGX_SCORES_F32 0
+#define PGX_SCORES_F16 1
+#define PGX_SCORES_BF16 2
+#define PGX_SHIELD_TIE_DISTANCE 1
+int pgx_shield_actions(pgx_env* env, int32_t flags, const void* scores, int32_t score_dtype, const int32_t* priority,
+                       void* actions, int32_t action_dtype, int32_t* next_xy, uint8_t* overridden, void* stream);
 
 /* Direction-to-goal planes (docs/SPEC.md S14), the "heuristic channels" of learned MAPF policies, read from the current
  * device state -- the state the next pgx_step reads, which this call does not change.  For every agent, window cell

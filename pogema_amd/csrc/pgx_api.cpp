@@ -1004,8 +1004,8 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
 }
 
 // The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
-// first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_goal_directions).  `who` names that
-// entry point in the error messages.
+// first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_goal_directions, pgx_shield_actions
+// with PGX_SHIELD_TIE_DISTANCE).  `who` names that entry point in the error messages.
 static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p) {
     const pgx_config& c = e->cfg;
     const pgx::CostToGoLayout l = pgx::cost_to_go_layout(c.batch, c.num_agents, c.height, c.width);
@@ -1073,6 +1073,50 @@ int pgx_pibt_actions(pgx_env* e, int32_t flags, const int32_t* priority, void* a
     p.actions = actions;
     p.next_xy = next_xy;
     PGX_HIP(pgx::launch_pibt(p, s));
+    return PGX_OK;
+}
+
+// ---- collision shielding (docs/SPEC.md S15) ---------------------------------------------------------------
+int pgx_shield_actions(pgx_env* e, int32_t flags, const void* scores, int32_t score_dtype, const int32_t* priority,
+                       void* actions, int32_t action_dtype, int32_t* next_xy, uint8_t* overridden, void* stream) {
+    static const char who[] = "pgx_shield_actions";
+    // the argument checks come first and need no device
+    if (!scores) return fail_msg(PGX_E_INVALID, "%s: scores is null", who);
+    if (!actions) return fail_msg(PGX_E_INVALID, "%s: actions is null", who);
+    if (const int rc = check_flags(who, flags, PGX_SHIELD_TIE_DISTANCE)) return rc;
+    static_assert(PGX_SCORES_F32 == pgx::SCORES_F32 && PGX_SCORES_F16 == pgx::SCORES_F16 &&
+                      PGX_SCORES_BF16 == pgx::SCORES_BF16, "the kernels' score codes are the header's");
+    if (score_dtype != PGX_SCORES_F32 && score_dtype != PGX_SCORES_F16 && score_dtype != PGX_SCORES_BF16)
+        return fail_msg(PGX_E_INVALID, "%s: bad score_dtype %d", who, score_dtype);
+    if (const int rc = check_action_dtype(who, action_dtype)) return rc;
+    static const size_t action_bytes[3] = {1, 4, 8};
+    if (const int rc = check_aligned(who, "scores", scores, score_dtype == PGX_SCORES_F32 ? 4 : 2)) return rc;
+    if (const int rc = check_aligned(who, "actions", actions, action_bytes[action_dtype])) return rc;
+    if (const int rc = check_aligned(who, "priority", priority, 4)) return rc;
+    if (const int rc = check_aligned(who, "next_xy", next_xy, 4)) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::ShieldParams p{};
+    if (flags & PGX_SHIELD_TIE_DISTANCE) {
+        pgx::CostToGoParams cp{};
+        if (const int rc = cost_to_go_cache(e, s, who, &cp)) return rc;
+        PGX_HIP(pgx::launch_cost_to_go_refresh(cp, s));
+        static_cast<pgx::StateView&>(p) = cp;
+        p.cell_bytes = cp.cell_bytes;
+        p.field = cp.field;
+        p.tie_distance = 1;
+    } else {
+        static_cast<pgx::StateView&>(p) = state_view(e);   // no cache, no allocation: one launch
+    }
+    p.action_dtype = action_dtype;
+    p.priority = priority;
+    p.actions = actions;
+    p.next_xy = next_xy;
+    p.score_dtype = score_dtype;
+    p.scores = scores;
+    p.overridden = overridden;
+    PGX_HIP(pgx::launch_shield(p, s));
     return PGX_OK;
 }
 

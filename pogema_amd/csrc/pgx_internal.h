@@ -346,4 +346,14 @@ struct PibtParams : StateView {
 };
 hipError_t launch_pibt(const PibtParams& p, hipStream_t stream);
 
+// ---- collision shielding (pgx_shield.hip): the planner over the caller's action scores ------------------------------
+enum { SCORES_F32 = 0, SCORES_F16 = 1, SCORES_BF16 = 2 };  // PGX_SCORES_* (include/pogema_amd.h)
+struct ShieldParams : PibtParams {   // `field` is null without `tie_distance`
+    int32_t score_dtype;     // SCORES_*
+    int32_t tie_distance;    // equal scores are ordered by the planner's key (PGX_SHIELD_TIE_DISTANCE)
+    const void* scores;      // [B][A][5] of score_dtype
+    uint8_t* overridden;     // [B][A], may be null
+};
+hipError_t launch_shield(const ShieldParams& p, hipStream_t stream);
+
 }  // namespace pgx

@@ -17,53 +17,15 @@
 //       cells (a reservation whose branch failed is the failed agent's own cell), so it is a set: open addressing,
 //       linear probing, 2^ceil(log2(2A)) words per env keyed by the packed cell, never more than half full, nothing is
 //       ever deleted.  The same table serves every legal map size (a dense H x W table would be 2 MB at 1024 x 1024).
-//       Phase 2 touches LDS only.
+//       Phase 2 touches LDS only.  It, the reservation set and the packed formats live in pgx_pibt_plan.h, shared
+//       with the collision shield (pgx_shield.hip), whose lanes order their candidates by the caller's scores.
 //   stores (parallel, every lane): action and next cell; unplanned agents get action 0 and their own cell.
-// LDS: 40 bytes per lane (10 KB / 40 KB), static.  The grid depends on batch and A only; nothing but the caller's
+// LDS: 40 bytes per lane + 256 (10.25 KB / 40.25 KB), static.  The grid depends on batch and A only; nothing but the caller's
 // outputs is written.
-#include "pgx_internal.h"
+#include "pgx_pibt_plan.h"
 
 namespace pgx {
 namespace {
-
-constexpr uint32_t PIBT_FAR = 0x7FFF7FFFu;    // staged position of an unplanned agent: no candidate cell equals it
-constexpr uint32_t PIBT_NO_CELL = 0xFFFFFFFEu;  // a candidate outside the map or on an obstacle
-constexpr uint32_t PIBT_EMPTY = 0xFFFFFFFFu;  // free word of the reservation set
-constexpr uint16_t PIBT_END = 0xFFFFu;        // end of a candidate list
-constexpr uint16_t PIBT_NONE = 0xFFFFu;       // no caller: the agent was started from the priority order
-constexpr uint8_t PIBT_UNSET = 0xFFu;         // `next` not decided yet
-constexpr unsigned long long PIBT_DROP = ~0ull;  // sort key of a candidate that is not kept
-constexpr uint32_t PIBT_INF = (1u << 21) - 1u;   // D of an unreachable cell inside the key: above every distance (< 2^20)
-
-__device__ __forceinline__ int pibt_dx(int a) { return (a == 2) - (a == 1); }  // MOVES: noop, up, down, left, right
-__device__ __forceinline__ int pibt_dy(int a) { return (a == 4) - (a == 3); }
-
-__device__ __forceinline__ void pibt_cswap(unsigned long long& a, unsigned long long& b) {
-    const unsigned long long lo = a < b ? a : b, hi = a < b ? b : a;
-    a = lo;
-    b = hi;
-}
-
-// the reservation set of one env: `set` has 1 << log2n words
-__device__ __forceinline__ bool pibt_reserved(const uint32_t* set, int log2n, uint32_t cell) {
-    const uint32_t mask = (1u << log2n) - 1u;
-    for (uint32_t h = (cell * 0x9E3779B1u) >> (32 - log2n);; h = (h + 1u) & mask) {
-        const uint32_t k = set[h];
-        if (k == cell) return true;
-        if (k == PIBT_EMPTY) return false;
-    }
-}
-__device__ __forceinline__ void pibt_reserve(uint32_t* set, int log2n, uint32_t cell) {
-    const uint32_t mask = (1u << log2n) - 1u;
-    for (uint32_t h = (cell * 0x9E3779B1u) >> (32 - log2n);; h = (h + 1u) & mask) {
-        const uint32_t k = set[h];
-        if (k == cell) return;
-        if (k == PIBT_EMPTY) {
-            set[h] = cell;
-            return;
-        }
-    }
-}
 
 template <int T, typename F>
 __global__ void __launch_bounds__(T) pibt_kernel(const PibtParams p, int epb, int log2n) {
@@ -169,50 +131,7 @@ __global__ void __launch_bounds__(T) pibt_kernel(const PibtParams p, int epb, in
     }
     __syncthreads();
 
-    // phase 2: lane e of wave 0 runs env e.  `cur` is the agent whose call is running; a call that succeeds ends the
-    // whole chain of its callers (each of them returns True at once), one that fails resumes its caller's loop.
-    if (t < nenv) {
-        const int b = t * A;
-        const int n = (int)s_n[t];
-        uint32_t* set = s_set + ((size_t)t << log2n);
-        int k = 0, cur = -1;
-        for (;;) {
-            if (cur < 0) {
-                if (k >= n) break;
-                const int c = s_order[b + k++];
-                if (s_act[b + c] != PIBT_UNSET) continue;
-                cur = c;
-                s_par[b + c] = PIBT_NONE;
-                s_ci[b + c] = 0;
-                continue;
-            }
-            const int ci = s_ci[b + cur];
-            const uint16_t e = ci < 5 ? s_cand[5 * (b + cur) + ci] : PIBT_END;
-            const uint32_t here = s_pos[b + cur];
-            const uint16_t par = s_par[b + cur];
-            if (e == PIBT_END) {              // every candidate refused: stay, and hold the own cell
-                s_act[b + cur] = 0;
-                pibt_reserve(set, log2n, here);
-                cur = par == PIBT_NONE ? -1 : (int)par;
-                continue;
-            }
-            s_ci[b + cur] = (uint8_t)(ci + 1);
-            const int a = e & 7;
-            const uint32_t v = (uint32_t)((int)here + pibt_dx(a) * 65536 + pibt_dy(a));
-            if (pibt_reserved(set, log2n, v)) continue;
-            if (par != PIBT_NONE && v == s_pos[b + par]) continue;
-            s_act[b + cur] = (uint8_t)a;
-            pibt_reserve(set, log2n, v);
-            const int j = e >> 4;
-            if ((e & 8) && s_act[b + j] == PIBT_UNSET) {  // the cell's agent has to move on first
-                s_par[b + j] = (uint16_t)cur;
-                s_ci[b + j] = 0;
-                cur = j;
-                continue;
-            }
-            cur = -1;
-        }
-    }
+    pibt_serial(PibtLds{s_pos, s_prio, s_set, s_cand, s_order, s_par, s_ci, s_act, s_n}, nenv, A, log2n);
     __syncthreads();
 
     if (have) {

@@ -207,6 +207,18 @@ class Pogema:
         actions, _ = vec.pibt_actions(priority=priority)
         return [int(a) for a in actions[0].cpu().numpy()]
 
+    def shield_actions(self, scores, priority=None):
+        """A policy's action scores made jointly collision-free (VecPogema.shield_actions), as a list for step().
+        `scores`: array-like [agents, 5], one score per agent and action, higher is better; `priority`: one integer per
+        agent, None = all equal."""
+        import torch
+        vec = self._vec
+        scores = torch.as_tensor(np.asarray(scores, dtype=np.float32)[None], device=vec.device)
+        if priority is not None:
+            priority = torch.as_tensor(np.asarray(priority, dtype=np.int64)[None], device=vec.device)
+        actions, _, _ = vec.shield_actions(scores, priority=priority)
+        return [int(a) for a in actions[0].cpu().numpy()]
+
     def _metrics_dict(self, values):
         from ._lib import METRIC_NAMES
         metrics = {k: float(x) for k, x in zip(METRIC_NAMES, values)}

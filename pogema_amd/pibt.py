@@ -8,7 +8,9 @@ import torch
 
 class PibtPolicy:
     """`act()` -> (actions, next_xy) for `env.step`; `update(rewards, episode_done)` after the step.  The int32 priority
-    tensor [batch, agents] lives on the env's device; nothing here synchronises with the host."""
+    tensor [batch, agents] lives on the env's device; nothing here synchronises with the host.
+    `act(scores=...)` shields a learnt policy's action scores under the same priorities (VecPogema.shield_actions,
+    docs/SPEC.md S15) and returns (actions, next_xy, overridden)."""
 
     def __init__(self, env):
         self.env = env
@@ -17,8 +19,12 @@ class PibtPolicy:
     def reset(self) -> None:
         self.priority.zero_()
 
-    def act(self, dtype=torch.int64, out=None):
-        return self.env.pibt_actions(priority=self.priority, dtype=dtype, out=out)
+    def act(self, dtype=torch.int64, out=None, *, scores=None, tie_break=None):
+        if scores is None:
+            if tie_break is not None:
+                raise ValueError("tie_break belongs to act(scores=...)")
+            return self.env.pibt_actions(priority=self.priority, dtype=dtype, out=out)
+        return self.env.shield_actions(scores, priority=self.priority, tie_break=tie_break, dtype=dtype, out=out)
 
     def update(self, rewards, episode_done=None) -> None:
         """Priority becomes 0 where the agent got a positive reward in this step, stands on its target, is inactive, or

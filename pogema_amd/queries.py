@@ -1,6 +1,6 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
-cooperative planner and direction-to-goal planes.  Each is one C-ABI call into caller-owned or fresh output tensors;
-query_output() is the one place an `out` tensor is checked or allocated.
+cooperative planner, collision shielding and direction-to-goal planes.  Each is one C-ABI call into caller-owned or fresh
+output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
 from __future__ import annotations
 
@@ -43,6 +43,8 @@ class QueryMixin:
     """The queries of a VecPogema.  Expects of the class it is mixed into: `_handle`, `_lib`, `device`, `batch`,
     `num_agents`, `window`, `_ACTION_CODE`, `_stream()`."""
 
+    _SCORE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # PGX_SCORES_* of shield_actions' scores
+
     def _action_dtypes(self, dtype, actions):
         """The dtypes the `actions` output may have: the caller's tensor decides, else `dtype`."""
         if actions is not None:
@@ -84,8 +86,8 @@ class QueryMixin:
 
     @property
     def cost_to_go_builds(self) -> int:
-        """Distance fields cost_to_go(), pibt_actions() and goal_directions() have built since this env was created
-        (synchronises the stream)."""
+        """Distance fields cost_to_go(), pibt_actions(), goal_directions() and shield_actions(tie_break="distance") have
+        built since this env was created (synchronises the stream)."""
         n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
         if n < 0:
             _lib.check(int(n))
@@ -115,6 +117,19 @@ class QueryMixin:
                                                 self._stream()))
         return index, offset, count
 
+    def _priority(self, priority):
+        """The planners' `priority` argument as a contiguous int32 tensor [batch, agents], or None."""
+        if priority is None:
+            return None
+        shape = (self.batch, self.num_agents)
+        if not isinstance(priority, torch.Tensor):
+            raise TypeError(f"priority must be a torch.Tensor or None, got {type(priority).__name__}")
+        if priority.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
+            raise TypeError(f"priority must be an integer tensor, got {priority.dtype}")
+        if tuple(priority.shape) != shape or priority.device != self.device:
+            raise ValueError(f"priority must have shape {shape} on {self.device}")
+        return priority.to(torch.int32).contiguous()
+
     def pibt_actions(self, priority=None, dtype=torch.int64, out=None):
         """Cooperative one-step planner (PIBT, docs/SPEC.md S13), computed on the device from the current state -- the
         state the next step() reads, which this call leaves untouched.  Returns (actions [batch, agents] of `dtype`,
@@ -129,14 +144,7 @@ class QueryMixin:
         stream-ordered, need no host sync and can be captured.  `out=(actions, next_xy)`: caller-owned contiguous
         tensors on this device (actions int8 / int32 / int64, next_xy int32)."""
         B, A = self.batch, self.num_agents
-        if priority is not None:
-            if not isinstance(priority, torch.Tensor):
-                raise TypeError(f"priority must be a torch.Tensor or None, got {type(priority).__name__}")
-            if priority.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
-                raise TypeError(f"priority must be an integer tensor, got {priority.dtype}")
-            if tuple(priority.shape) != (B, A) or priority.device != self.device:
-                raise ValueError(f"priority must have shape {(B, A)} on {self.device}")
-            priority = priority.to(torch.int32).contiguous()
+        priority = self._priority(priority)
         actions, next_xy = _split(out, ("actions", "next_xy"))
         actions = query_output("out[actions]", actions, self._action_dtypes(dtype, actions), (B, A), self.device)
         next_xy = query_output("out[next_xy]", next_xy, torch.int32, (B, A, 2), self.device)
@@ -144,6 +152,46 @@ class QueryMixin:
                                               actions.data_ptr(), self._ACTION_CODE[actions.dtype], next_xy.data_ptr(),
                                               self._stream()))
         return actions, next_xy
+
+    def shield_actions(self, scores, priority=None, tie_break=None, dtype=torch.int64, out=None):
+        """Collision shielding (docs/SPEC.md S15): pibt_actions()' planner with every agent's candidate cells ordered by
+        a policy's action scores instead of by the distance to its target -- each active agent gets the best-scored
+        action that is jointly collision-free.  Computed on the device from the current state, which the call leaves
+        untouched.  Returns (actions [batch, agents] of `dtype`, next_xy int32 [batch, agents, 2], overridden uint8
+        [batch, agents]: 1 where an active agent's action is not the argmax of its scores).
+        `scores`: float32 / float16 / bfloat16 [batch, agents, 5] on this device (made contiguous if it is not), one
+        score per action, higher is better; then the lower action.  -0.0 equals +0.0, infinities are ordinary values, a
+        NaN ranks lowest.  Moves off the map or into an obstacle are dropped whatever their score, so the call is also
+        the action mask.  pibt_actions()' guarantees (no shared next cell, no swap, under collision_system="soft" every
+        active agent lands on its next_xy) hold for any scores.  The call is deterministic; to sample, pass
+        `logits + gumbel_noise`: taking candidates in that order is Plackett-Luce sampling without replacement.
+        `priority`: as in pibt_actions().  `tie_break`: None, or "distance": equal scores are ordered as pibt_actions()
+        orders its candidates (with constant scores the result is pibt_actions()' exactly).
+        tie_break=None reads no distance field: one launch that allocates nothing, stream-ordered, no host sync,
+        capturable in a HIP graph from the first call.  tie_break="distance" shares cost_to_go()'s cache under
+        pibt_actions()' rules (whichever call is first allocates it, not inside a graph capture).
+        `out=(actions, next_xy, overridden)`: caller-owned contiguous tensors on this device (actions int8 / int32 /
+        int64, next_xy int32, overridden uint8)."""
+        B, A = self.batch, self.num_agents
+        if not isinstance(scores, torch.Tensor):
+            raise TypeError(f"scores must be a torch.Tensor, got {type(scores).__name__}")
+        if scores.dtype not in self._SCORE_CODE:
+            raise TypeError(f"scores must be a float32, float16 or bfloat16 tensor, got {scores.dtype}")
+        if tuple(scores.shape) != (B, A, 5) or scores.device != self.device:
+            raise ValueError(f"scores must have shape {(B, A, 5)} on {self.device}")
+        if tie_break not in _lib.SHIELD_TIE_BREAKS:
+            raise ValueError(f"tie_break must be None or 'distance', got {tie_break!r}")
+        scores = scores.contiguous()
+        priority = self._priority(priority)
+        actions, next_xy, overridden = _split(out, ("actions", "next_xy", "overridden"))
+        actions = query_output("out[actions]", actions, self._action_dtypes(dtype, actions), (B, A), self.device)
+        next_xy = query_output("out[next_xy]", next_xy, torch.int32, (B, A, 2), self.device)
+        overridden = query_output("out[overridden]", overridden, torch.uint8, (B, A), self.device)
+        _lib.check(self._lib.pgx_shield_actions(self._handle, _lib.SHIELD_TIE_BREAKS[tie_break], scores.data_ptr(),
+                                                self._SCORE_CODE[scores.dtype], priority.data_ptr() if priority is not None else None,
+                                                actions.data_ptr(), self._ACTION_CODE[actions.dtype], next_xy.data_ptr(),
+                                                overridden.data_ptr(), self._stream()))
+        return actions, next_xy, overridden
 
     def goal_directions(self, format: str = "float32", out=None) -> torch.Tensor:
         """Direction-to-goal planes (docs/SPEC.md S14), the "heuristic channels" of DHC-style policies, computed on the
