@@ -379,8 +379,8 @@ int pgx_cost_to_go(pgx_env* env, int32_t flags, int32_t* out, void* stream);
  * rounded up to a multiple of 16 + 4 * B * A (target tags) + 4 * B * H * ceil(W / 32) (map copies).  Returns the status
  * code of pgx_check_config for a configuration it refuses. */
 int64_t pgx_cost_to_go_bytes(const pgx_config* cfg);
-/* Distance fields pgx_cost_to_go, pgx_pibt_actions, pgx_goal_directions and pgx_shield_actions have built since the
- * handle was created (0 before the first call of any of them).  Synchronises `stream`. */
+/* Distance fields pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_goal_directions and pgx_shield_actions have
+ * built since the handle was created (0 before the first call of any of them).  Synchronises `stream`. */
 int64_t pgx_cost_to_go_builds(pgx_env* env, void* stream);
 
 /* Neighbour lists (docs/SPEC.md S12), read from the current device state -- the state the next pgx_step reads, which
@@ -427,6 +427,39 @@ int pgx_visible_agents(pgx_env* env, int32_t k, int32_t flags, int32_t* index, i
  * reset, like pgx_step. */
 int pgx_pibt_actions(pgx_env* env, int32_t flags, const int32_t* priority, void* actions, int32_t action_dtype,
                      int32_t* next_xy, void* stream);
+
+/* Multi-step planner (docs/SPEC.md S16): pgx_pibt_actions' planner iterated `horizon` times inside one launch, on a
+ * private copy of the positions -- the call reads the current device state and changes none of it.  The targets and
+ * their distance fields are held for the whole lookahead.  Step h plans from the cells step h - 1 sent the agents to;
+ * the agents planned at step 0 are those with bit 0 of is_active set, and under PGX_ON_TARGET_FINISH an agent stops
+ * being planned once its next cell is its target (under the other two modes it stays planned, on the same target).  An
+ * agent's priority becomes 0 when it is not planned any more or its next cell is its target and grows by 1 (two's
+ * complement wrap) otherwise -- the textbook growing priorities.  pgx_pibt_actions' guarantees hold for every step.
+ *   flags         0, or PGX_PLAN_FIXED_PRIORITY: the priorities stay as given for the whole lookahead
+ *   horizon       K, 1..PGX_MAX_PLAN_HORIZON
+ *   priority      device i32 [batch, agents], the priorities of step 0; NULL: all 0
+ *   actions       device [K, batch, agents] of action_dtype (PGX_ACTION_*), the layout pgx_rollout reads.  Must not be
+ *                 NULL.
+ *   path_xy       device i32 [K, batch, agents, 2]: the cell step h sends each agent to, unpadded (row, col); an agent
+ *                 that is not planned keeps its cell.  May be NULL.
+ *   arrival       device i32 [batch, agents]: for an agent planned at step 0 the smallest h in 0..K such that it stands
+ *                 on its target after h steps (0: it stands there now), -1 when there is none; -1 for every other agent.
+ *                 May be NULL.
+ *   priority_out  device i32 [batch, agents]: the priorities after step K - 1, to continue from.  May be NULL.
+ * With horizon = 1, actions and path_xy are pgx_pibt_actions' outputs.  Under PGX_COLLISION_SOFT with
+ * PGX_ON_TARGET_FINISH or PGX_ON_TARGET_NOTHING a pgx_rollout of `actions` puts every agent on path_xy[h] after step h
+ * for as long as the env's episode lasts (the plan knows neither the step limit nor auto-reset); under
+ * PGX_ON_TARGET_RESTART the plan is exact up to the first arrival in the env (the engine then draws a target the plan
+ * cannot know); under the other collision systems pgx_pibt_actions' caveat applies from the first reverted move on.
+ * Shares pgx_cost_to_go's distance-field cache under pgx_pibt_actions' rules: ONE refresh per call whatever K is, then
+ * one more launch; whichever entry point that uses the cache is called first allocates it -- inside a graph capture
+ * that first call returns PGX_E_STATE.  Afterwards asynchronous on `stream`, no host sync, capturable in a HIP graph.
+ * PGX_E_INVALID for a NULL `actions`, unknown flag bits, a horizon outside its range, a bad action_dtype or a misaligned
+ * pointer (checked before the handle: no device needed); PGX_E_STATE before the first reset, like pgx_step. */
+#define PGX_PLAN_FIXED_PRIORITY 1
+#define PGX_MAX_PLAN_HORIZON 256
+int pgx_pibt_plan(pgx_env* env, int32_t flags, int32_t horizon, const int32_t* priority, void* actions,
+                  int32_t action_dtype, int32_t* path_xy, int32_t* arrival, int32_t* priority_out, void* stream);
 
 /* Collision shielding (docs/SPEC.md S15): pgx_pibt_actions' planner -- the same planned agents, serving order
  * (-priority, index), priority inheritance, backtracking, outputs and guarantees -- with every agent's candidate cells

@@ -57,6 +57,8 @@ MAX_OBS_RADIUS, MAX_AGENTS, MAX_SIDE = 15, 1024, 1024
 MAX_NEIGHBOURS = 32  # PGX_MAX_NEIGHBOURS: entries per agent of pgx_visible_agents
 DIRECTIONS_FORMATS = {"float32": 0, "uint8": 1, "bits": 2}  # PGX_DIRECTIONS_*: formats of pgx_goal_directions
 SHIELD_TIE_BREAKS = {None: 0, "distance": 1}  # flags of pgx_shield_actions (PGX_SHIELD_TIE_DISTANCE)
+MAX_PLAN_HORIZON = 256  # PGX_MAX_PLAN_HORIZON: steps of one pgx_pibt_plan
+PLAN_FIXED_PRIORITY = 1  # PGX_PLAN_FIXED_PRIORITY: flag of pgx_pibt_plan
 
 
 # every symbol include/pogema_amd.h declares; tests/test_abi.py checks the library exports them all
@@ -68,7 +70,7 @@ EXPORTED_SYMBOLS = (
     "pgx_np_streams", "pgx_np_streams_host", "pgx_np_generate", "pgx_np_generate_host", "pgx_rollout", "pgx_buffers_stride", "pgx_buffers_drop", "pgx_xcd_shares", "pgx_xcd_tune", "pgx_buffers_create_at", "pgx_time_observe_pair", "pgx_buffers_va_reserved", "pgx_get_geometry",
     "pgx_expert_actions", "pgx_set_map_pool", "pgx_reset_pool", "pgx_regenerate_pool", "pgx_get_map_index",
     "pgx_cost_to_go", "pgx_cost_to_go_bytes", "pgx_cost_to_go_builds", "pgx_visible_agents", "pgx_pibt_actions",
-    "pgx_goal_directions", "pgx_shield_actions",
+    "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan",
 )
 
 
@@ -188,6 +190,8 @@ def load() -> C.CDLL:
     lib.pgx_visible_agents.restype = C.c_int
     lib.pgx_pibt_actions.argtypes = [vp, i32, vp, vp, i32, vp, vp]
     lib.pgx_pibt_actions.restype = C.c_int
+    lib.pgx_pibt_plan.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
+    lib.pgx_pibt_plan.restype = C.c_int
     lib.pgx_goal_directions.argtypes = [vp, i32, vp, i32, vp]
     lib.pgx_goal_directions.restype = C.c_int
     lib.pgx_shield_actions.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp]

@@ -134,7 +134,7 @@ struct pgx_env {
     DevBuf<uint32_t> pool_cap;            // [M] start/target pairs each map can hold
     DevBuf<int32_t> map_index;            // [B] pool index of each env's map, -1 after a non-pool install
     // cost-to-go cache (docs/SPEC.md S11, pgx::cost_to_go_layout), allocated by the first pgx_cost_to_go,
-    // pgx_pibt_actions or pgx_goal_directions
+    // pgx_pibt_actions, pgx_pibt_plan or pgx_goal_directions
     DevBuf<uint8_t> c2g;
 };
 
@@ -1004,8 +1004,8 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
 }
 
 // The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
-// first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_goal_directions, pgx_shield_actions
-// with PGX_SHIELD_TIE_DISTANCE).  `who` names that entry point in the error messages.
+// first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_goal_directions,
+// pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE).  `who` names that entry point in the error messages.
 static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p) {
     const pgx_config& c = e->cfg;
     const pgx::CostToGoLayout l = pgx::cost_to_go_layout(c.batch, c.num_agents, c.height, c.width);
@@ -1073,6 +1073,45 @@ int pgx_pibt_actions(pgx_env* e, int32_t flags, const int32_t* priority, void* a
     p.actions = actions;
     p.next_xy = next_xy;
     PGX_HIP(pgx::launch_pibt(p, s));
+    return PGX_OK;
+}
+
+// ---- multi-step planner (docs/SPEC.md S16) ----------------------------------------------------------------
+int pgx_pibt_plan(pgx_env* e, int32_t flags, int32_t horizon, const int32_t* priority, void* actions, int32_t action_dtype,
+                  int32_t* path_xy, int32_t* arrival, int32_t* priority_out, void* stream) {
+    static const char who[] = "pgx_pibt_plan";
+    // the argument checks come first and need no device
+    if (!actions) return fail_msg(PGX_E_INVALID, "%s: actions is null", who);
+    if (const int rc = check_flags(who, flags, PGX_PLAN_FIXED_PRIORITY)) return rc;
+    if (horizon < 1 || horizon > PGX_MAX_PLAN_HORIZON)
+        return fail_msg(PGX_E_INVALID, "%s: horizon %d is outside 1..%d", who, horizon, PGX_MAX_PLAN_HORIZON);
+    if (const int rc = check_action_dtype(who, action_dtype)) return rc;
+    static const size_t action_bytes[3] = {1, 4, 8};
+    if (const int rc = check_aligned(who, "actions", actions, action_bytes[action_dtype])) return rc;
+    if (const int rc = check_aligned(who, "priority", priority, 4)) return rc;
+    if (const int rc = check_aligned(who, "path_xy", path_xy, 4)) return rc;
+    if (const int rc = check_aligned(who, "arrival", arrival, 4)) return rc;
+    if (const int rc = check_aligned(who, "priority_out", priority_out, 4)) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::CostToGoParams cp{};
+    if (const int rc = cost_to_go_cache(e, s, who, &cp)) return rc;
+    PGX_HIP(pgx::launch_cost_to_go_refresh(cp, s));    // once: the targets are held for the whole lookahead
+    pgx::PibtPlanParams p{};
+    static_cast<pgx::StateView&>(p) = cp;
+    p.action_dtype = action_dtype;
+    p.cell_bytes = cp.cell_bytes;
+    p.field = cp.field;
+    p.priority = priority;
+    p.actions = actions;
+    p.horizon = horizon;
+    p.finish = e->cfg.on_target == PGX_ON_TARGET_FINISH ? 1 : 0;
+    p.fixed_priority = (flags & PGX_PLAN_FIXED_PRIORITY) ? 1 : 0;
+    p.path_xy = path_xy;
+    p.arrival = arrival;
+    p.priority_out = priority_out;
+    PGX_HIP(pgx::launch_pibt_plan(p, s));
     return PGX_OK;
 }
 

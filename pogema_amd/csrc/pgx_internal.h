@@ -346,6 +346,17 @@ struct PibtParams : StateView {
 };
 hipError_t launch_pibt(const PibtParams& p, hipStream_t stream);
 
+// ---- multi-step planner (pgx_pibt_horizon.hip): the planner iterated over a horizon in one launch ----------------
+struct PibtPlanParams : PibtParams {   // `actions` is [horizon][B][A]; `next_xy` is not used
+    int32_t horizon;         // steps of the lookahead, 1..PGX_MAX_PLAN_HORIZON
+    int32_t finish;          // on_target = finish: an agent that reaches its target is not planned any more
+    int32_t fixed_priority;  // the priorities are held instead of grown (PGX_PLAN_FIXED_PRIORITY)
+    int32_t* path_xy;        // [horizon][B][A][2] unpadded, may be null
+    int32_t* arrival;        // [B][A], may be null
+    int32_t* priority_out;   // [B][A], may be null
+};
+hipError_t launch_pibt_plan(const PibtPlanParams& p, hipStream_t stream);
+
 // ---- collision shielding (pgx_shield.hip): the planner over the caller's action scores ------------------------------
 enum { SCORES_F32 = 0, SCORES_F16 = 1, SCORES_BF16 = 2 };  // PGX_SCORES_* (include/pogema_amd.h)
 struct ShieldParams : PibtParams {   // `field` is null without `tie_distance`

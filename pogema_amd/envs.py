@@ -207,6 +207,17 @@ class Pogema:
         actions, _ = vec.pibt_actions(priority=priority)
         return [int(a) for a in actions[0].cpu().numpy()]
 
+    def pibt_plan(self, horizon, priority=None):
+        """The cooperative planner's actions for the next `horizon` steps (VecPogema.pibt_plan), as one list per step
+        for step().  `priority`: one integer per agent for the first step, None = all equal; they grow inside the
+        lookahead."""
+        import torch
+        vec = self._vec
+        if priority is not None:
+            priority = torch.as_tensor(np.asarray(priority, dtype=np.int64)[None], device=vec.device)
+        actions = vec.pibt_plan(horizon, priority=priority)[0]
+        return [[int(a) for a in row] for row in actions[:, 0].cpu().numpy()]
+
     def shield_actions(self, scores, priority=None):
         """A policy's action scores made jointly collision-free (VecPogema.shield_actions), as a list for step().
         `scores`: array-like [agents, 5], one score per agent and action, higher is better; `priority`: one integer per

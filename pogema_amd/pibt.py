@@ -10,7 +10,9 @@ class PibtPolicy:
     """`act()` -> (actions, next_xy) for `env.step`; `update(rewards, episode_done)` after the step.  The int32 priority
     tensor [batch, agents] lives on the env's device; nothing here synchronises with the host.
     `act(scores=...)` shields a learnt policy's action scores under the same priorities (VecPogema.shield_actions,
-    docs/SPEC.md S15) and returns (actions, next_xy, overridden)."""
+    docs/SPEC.md S15) and returns (actions, next_xy, overridden).
+    `plan(horizon)` -> (actions, path_xy, arrival) for `env.rollout`: the same priorities grown inside the lookahead
+    (VecPogema.pibt_plan, docs/SPEC.md S16); no `update()` is needed between a plan and the next."""
 
     def __init__(self, env):
         self.env = env
@@ -25,6 +27,17 @@ class PibtPolicy:
                 raise ValueError("tie_break belongs to act(scores=...)")
             return self.env.pibt_actions(priority=self.priority, dtype=dtype, out=out)
         return self.env.shield_actions(scores, priority=self.priority, tie_break=tie_break, dtype=dtype, out=out)
+
+    def plan(self, horizon, dtype=torch.int64, out=None):
+        """`horizon` steps planned ahead from the current state under `self.priority`; the priorities the lookahead
+        ends with replace it, so that the next plan() or act() after `env.rollout(actions)` continues where this one
+        stopped.  The plan does not know when an episode ends: where the rollout reports `episode_done` for an env (its
+        time limit, or every agent finished), zero that env's row of `self.priority` before planning again, as
+        `update(rewards, episode_done)` does.  `out=(actions, path_xy, arrival, priority)` as VecPogema.pibt_plan takes
+        it."""
+        actions, path_xy, arrival, self.priority = self.env.pibt_plan(horizon, priority=self.priority, dtype=dtype,
+                                                                     out=out)
+        return actions, path_xy, arrival
 
     def update(self, rewards, episode_done=None) -> None:
         """Priority becomes 0 where the agent got a positive reward in this step, stands on its target, is inactive, or

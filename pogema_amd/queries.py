@@ -1,6 +1,6 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
-cooperative planner, collision shielding and direction-to-goal planes.  Each is one C-ABI call into caller-owned or fresh
-output tensors; query_output() is the one place an `out` tensor is checked or allocated.
+cooperative planner and its multi-step lookahead, collision shielding and direction-to-goal planes.  Each is one C-ABI
+call into caller-owned or fresh output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
 from __future__ import annotations
 
@@ -86,8 +86,8 @@ class QueryMixin:
 
     @property
     def cost_to_go_builds(self) -> int:
-        """Distance fields cost_to_go(), pibt_actions(), goal_directions() and shield_actions(tie_break="distance") have
-        built since this env was created (synchronises the stream)."""
+        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), goal_directions() and
+        shield_actions(tie_break="distance") have built since this env was created (synchronises the stream)."""
         n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
         if n < 0:
             _lib.check(int(n))
@@ -152,6 +152,45 @@ class QueryMixin:
                                               actions.data_ptr(), self._ACTION_CODE[actions.dtype], next_xy.data_ptr(),
                                               self._stream()))
         return actions, next_xy
+
+    def pibt_plan(self, horizon, priority=None, growing: bool = True, dtype=torch.int64, out=None):
+        """Multi-step planner (docs/SPEC.md S16): pibt_actions()' planner iterated `horizon` times in one launch, on a
+        private copy of the positions -- computed on the device from the current state, which the call leaves untouched.
+        Step h plans from the cells step h - 1 sent the agents to; the targets are held for the whole lookahead.  Under
+        on_target="finish" an agent is no longer planned once it has reached its target; under "nothing" and "restart" it
+        stays planned on the same target.  Returns
+            (actions [horizon, batch, agents] of `dtype`: what rollout(actions) takes;
+             path_xy int32 [horizon, batch, agents, 2]: the cell each step sends each agent to, unpadded (row, col);
+             arrival int32 [batch, agents]: the first h in 0..horizon after which the agent stands on its target, -1 when
+                 it does not within the horizon or was inactive at the start;
+             priority int32 [batch, agents]: the priorities after the last step, to continue from).
+        `growing=True`: the textbook priorities, PibtPolicy.update()'s rule -- 0 when the agent's next cell is its target
+        or it is not planned any more, else + 1 per step; False: `priority` is held for all steps.  pibt_actions()'
+        guarantees hold for every step; with horizon = 1, actions[0] and path_xy[0] are pibt_actions()' outputs.
+        Under collision_system="soft" with on_target "finish" or "nothing", rollout(actions) puts every agent on
+        path_xy[h] after step h until the env's episode ends (the plan ignores max_episode_steps and auto-reset).  Under
+        "restart" the plan is exact up to the first arrival in the env; under "priority" / "block_both" up to the first
+        reverted move.
+        `horizon`: an integer in 1..MAX_PLAN_HORIZON (256).  `priority`: as in pibt_actions().
+        Shares cost_to_go()'s cache under pibt_actions()' rules, with one refresh per call whatever the horizon is.
+        `out=(actions, path_xy, arrival, priority)`: caller-owned contiguous tensors on this device (actions int8 /
+        int32 / int64, the others int32)."""
+        B, A = self.batch, self.num_agents
+        if (isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer))
+                or not 1 <= horizon <= _lib.MAX_PLAN_HORIZON):
+            raise ValueError(f"horizon must be an integer in 1..{_lib.MAX_PLAN_HORIZON}, got {horizon!r}")
+        K = int(horizon)
+        priority = self._priority(priority)
+        actions, path_xy, arrival, priority_out = _split(out, ("actions", "path_xy", "arrival", "priority"))
+        actions = query_output("out[actions]", actions, self._action_dtypes(dtype, actions), (K, B, A), self.device)
+        path_xy = query_output("out[path_xy]", path_xy, torch.int32, (K, B, A, 2), self.device)
+        arrival = query_output("out[arrival]", arrival, torch.int32, (B, A), self.device)
+        priority_out = query_output("out[priority]", priority_out, torch.int32, (B, A), self.device)
+        _lib.check(self._lib.pgx_pibt_plan(self._handle, 0 if growing else _lib.PLAN_FIXED_PRIORITY, K,
+                                           priority.data_ptr() if priority is not None else None, actions.data_ptr(),
+                                           self._ACTION_CODE[actions.dtype], path_xy.data_ptr(), arrival.data_ptr(),
+                                           priority_out.data_ptr(), self._stream()))
+        return actions, path_xy, arrival, priority_out
 
     def shield_actions(self, scores, priority=None, tie_break=None, dtype=torch.int64, out=None):
         """Collision shielding (docs/SPEC.md S15): pibt_actions()' planner with every agent's candidate cells ordered by
