@@ -491,6 +491,43 @@ int pgx_pibt_plan(pgx_env* env, int32_t flags, int32_t horizon, const int32_t* p
 int pgx_shield_actions(pgx_env* env, int32_t flags, const void* scores, int32_t score_dtype, const int32_t* priority,
                        void* actions, int32_t action_dtype, int32_t* next_xy, uint8_t* overridden, void* stream);
 
+/* Move outcomes (docs/SPEC.md S17): what the move phase of pgx_step(actions) would do to every agent, and why a move
+ * that fails does, read from the current device state -- the state the next pgx_step reads, which this call does not
+ * change.  The engine's collision system and soft_vertex_rule apply.  An action outside 0..4 counts as 0 whatever
+ * bad_action says: the call never fails for it and never moves pgx_bad_action_count.  With cur the agent's cell,
+ * d = cur + MOVES[action], a mover = an agent with bit 0 of is_active set and an action of 1..4, o = the lowest-index
+ * active agent standing on d, and next = the cell the agent stands on after the move phase (cur or d), the code of an
+ * agent is the first that applies:
+ *   PGX_OUTCOME_STAY       not a mover (inactive, noop, out-of-range action)
+ *   PGX_OUTCOME_MOVED      next == d
+ *   PGX_OUTCOME_OBSTACLE   d is an obstacle (the ring around the map included)
+ *   PGX_OUTCOME_SWAP       o exists, is a mover and its d is this agent's cur
+ *   PGX_OUTCOME_OCCUPIED   o exists and stays where it is
+ *   PGX_OUTCOME_FOLLOW     o exists and leaves, no other mover claims d, and the collision system forbids following
+ *   PGX_OUTCOME_CONTESTED  otherwise: another mover claims d
+ *   actions   device [batch, agents] of action_dtype (PGX_ACTION_*), as pgx_step takes them.  Must not be NULL.
+ *   flags     reserved, must be 0
+ *   next_xy   device i32 [batch, agents, 2]: next, unpadded (row, col); an inactive agent's own cell.  May be NULL.
+ *   outcome   device u8 [batch, agents]: the code.  May be NULL.
+ *   blocker   device i32 [batch, agents]: o for SWAP, OCCUPIED and FOLLOW; for CONTESTED the lowest-index other mover
+ *             that claims d; -1 otherwise.  May be NULL.
+ *   counts    device i32 [batch, PGX_NUM_OUTCOMES]: active agents of the env per code; a row sums to the env's number
+ *             of active agents.  May be NULL.
+ * At least one output must not be NULL.  One kernel launch: allocates nothing (the first call included), asynchronous
+ * on `stream`, no host sync, capturable in a HIP graph from the first call.  PGX_E_INVALID for a NULL `actions`, four
+ * NULL outputs, non-zero flags, a bad action_dtype or a misaligned pointer (checked before the handle: no device
+ * needed); PGX_E_STATE before the first reset, like pgx_step. */
+#define PGX_OUTCOME_STAY 0
+#define PGX_OUTCOME_MOVED 1
+#define PGX_OUTCOME_OBSTACLE 2
+#define PGX_OUTCOME_SWAP 3
+#define PGX_OUTCOME_OCCUPIED 4
+#define PGX_OUTCOME_FOLLOW 5
+#define PGX_OUTCOME_CONTESTED 6
+#define PGX_NUM_OUTCOMES 7
+int pgx_move_outcomes(pgx_env* env, const void* actions, int32_t action_dtype, int32_t flags, int32_t* next_xy,
+                      uint8_t* outcome, int32_t* blocker, int32_t* counts, void* stream);
+
 /* Direction-to-goal planes (docs/SPEC.md S14), the "heuristic channels" of learned MAPF policies, read from the current
  * device state -- the state the next pgx_step reads, which this call does not change.  For every agent, window cell
  * (u, v) = map cell c = (x - r + u, y - r + v) in the orientation of observation plane 0, and move a of 1..4 (up, down,

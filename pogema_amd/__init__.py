@@ -6,8 +6,9 @@ from .grid_config import (GridConfig, Easy8x8, Normal8x8, Hard8x8, Easy16x16, Ha
 __version__ = "0.1.0"
 
 from .semantics import Semantics
+from ._lib import OUTCOMES, NUM_OUTCOMES  # the codes of move_outcomes(), index = code
 
-__all__ = ["GridConfig", "Semantics", "release_cached_buffers", "VecPogema", "PipelinedVecPogema", "PibtPolicy", "Pogema", "pogema_v0", "Easy8x8", "Normal8x8", "Hard8x8", "Easy16x16",
+__all__ = ["GridConfig", "Semantics", "OUTCOMES", "NUM_OUTCOMES", "release_cached_buffers", "VecPogema", "PipelinedVecPogema", "PibtPolicy", "Pogema", "pogema_v0", "Easy8x8", "Normal8x8", "Hard8x8", "Easy16x16",
            "Hard16x16", "Easy32x32", "Hard32x32", "Easy64x64", "Hard64x64"]
 
 

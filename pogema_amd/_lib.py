@@ -59,6 +59,9 @@ DIRECTIONS_FORMATS = {"float32": 0, "uint8": 1, "bits": 2}  # PGX_DIRECTIONS_*: 
 SHIELD_TIE_BREAKS = {None: 0, "distance": 1}  # flags of pgx_shield_actions (PGX_SHIELD_TIE_DISTANCE)
 MAX_PLAN_HORIZON = 256  # PGX_MAX_PLAN_HORIZON: steps of one pgx_pibt_plan
 PLAN_FIXED_PRIORITY = 1  # PGX_PLAN_FIXED_PRIORITY: flag of pgx_pibt_plan
+# PGX_OUTCOME_*: the codes of pgx_move_outcomes, index = code (docs/SPEC.md S17)
+OUTCOMES = ("STAY", "MOVED", "OBSTACLE", "SWAP", "OCCUPIED", "FOLLOW", "CONTESTED")
+NUM_OUTCOMES = len(OUTCOMES)  # PGX_NUM_OUTCOMES
 
 
 # every symbol include/pogema_amd.h declares; tests/test_abi.py checks the library exports them all
@@ -70,7 +73,7 @@ EXPORTED_SYMBOLS = (
     "pgx_np_streams", "pgx_np_streams_host", "pgx_np_generate", "pgx_np_generate_host", "pgx_rollout", "pgx_buffers_stride", "pgx_buffers_drop", "pgx_xcd_shares", "pgx_xcd_tune", "pgx_buffers_create_at", "pgx_time_observe_pair", "pgx_buffers_va_reserved", "pgx_get_geometry",
     "pgx_expert_actions", "pgx_set_map_pool", "pgx_reset_pool", "pgx_regenerate_pool", "pgx_get_map_index",
     "pgx_cost_to_go", "pgx_cost_to_go_bytes", "pgx_cost_to_go_builds", "pgx_visible_agents", "pgx_pibt_actions",
-    "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan",
+    "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan", "pgx_move_outcomes",
 )
 
 
@@ -196,6 +199,8 @@ def load() -> C.CDLL:
     lib.pgx_goal_directions.restype = C.c_int
     lib.pgx_shield_actions.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp]
     lib.pgx_shield_actions.restype = C.c_int
+    lib.pgx_move_outcomes.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.pgx_move_outcomes.restype = C.c_int
     lib.pgx_set_map_pool.argtypes = [vp, vp, i32, vp, vp]
     lib.pgx_set_map_pool.restype = C.c_int
     lib.pgx_reset_pool.argtypes = [vp, u64, vp, i32, vp]

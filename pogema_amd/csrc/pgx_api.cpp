@@ -1159,6 +1159,37 @@ int pgx_shield_actions(pgx_env* e, int32_t flags, const void* scores, int32_t sc
     return PGX_OK;
 }
 
+// ---- move outcomes (docs/SPEC.md S17) -----------------------------------------------------------------------
+int pgx_move_outcomes(pgx_env* e, const void* actions, int32_t action_dtype, int32_t flags, int32_t* next_xy,
+                      uint8_t* outcome, int32_t* blocker, int32_t* counts, void* stream) {
+    static const char who[] = "pgx_move_outcomes";
+    // the argument checks come first and need no device
+    if (!actions) return fail_msg(PGX_E_INVALID, "%s: actions is null", who);
+    if (!next_xy && !outcome && !blocker && !counts) return fail_msg(PGX_E_INVALID, "%s: every output is null", who);
+    if (const int rc = check_flags(who, flags, 0)) return rc;
+    if (const int rc = check_action_dtype(who, action_dtype)) return rc;
+    static const size_t action_bytes[3] = {1, 4, 8};
+    if (const int rc = check_aligned(who, "actions", actions, action_bytes[action_dtype])) return rc;
+    if (const int rc = check_aligned(who, "next_xy", next_xy, 4)) return rc;
+    if (const int rc = check_aligned(who, "blocker", blocker, 4)) return rc;
+    if (const int rc = check_aligned(who, "counts", counts, 4)) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    static_assert(PGX_COLLISION_PRIORITY == pgx::COLLISION_PRIORITY && PGX_COLLISION_BLOCK_BOTH == pgx::COLLISION_BLOCK_BOTH &&
+                      PGX_COLLISION_SOFT == pgx::COLLISION_SOFT, "the kernels' collision codes are the header's");
+    pgx::OutcomeParams p{state_view(e)};
+    p.collision = e->cfg.collision_system;
+    p.all_stay = e->cfg.soft_vertex_rule == PGX_SOFT_ALL_STAY ? 1 : 0;
+    p.action_dtype = action_dtype;
+    p.actions = actions;
+    p.next_xy = next_xy;
+    p.outcome = outcome;
+    p.blocker = blocker;
+    p.counts = counts;
+    PGX_HIP(pgx::launch_move_outcomes(p, (hipStream_t)stream));
+    return PGX_OK;
+}
+
 // ---- direction-to-goal planes (docs/SPEC.md S14) ----------------------------------------------------------
 int pgx_goal_directions(pgx_env* e, int32_t flags, void* out, int32_t format, void* stream) {
     static const char who[] = "pgx_goal_directions";

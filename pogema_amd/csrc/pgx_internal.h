@@ -367,4 +367,17 @@ struct ShieldParams : PibtParams {   // `field` is null without `tie_distance`
 };
 hipError_t launch_shield(const ShieldParams& p, hipStream_t stream);
 
+// ---- move outcomes (pgx_outcomes.hip): the resolve phase of the step as a read-only query ---------------------------
+struct OutcomeParams : StateView {
+    int32_t collision;       // COLLISION_*
+    int32_t all_stay;        // soft: every claimant of a contested cell stays (PGX_SOFT_ALL_STAY)
+    int32_t action_dtype;    // PGX_ACTION_*
+    const void* actions;     // [B][A] of action_dtype
+    int32_t* next_xy;        // [B][A][2] unpadded, may be null
+    uint8_t* outcome;        // [B][A] PGX_OUTCOME_*, may be null
+    int32_t* blocker;        // [B][A], may be null
+    int32_t* counts;         // [B][PGX_NUM_OUTCOMES], may be null
+};
+hipError_t launch_move_outcomes(const OutcomeParams& p, hipStream_t stream);
+
 }  // namespace pgx

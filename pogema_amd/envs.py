@@ -230,6 +230,15 @@ class Pogema:
         actions, _, _ = vec.shield_actions(scores, priority=priority)
         return [int(a) for a in actions[0].cpu().numpy()]
 
+    def move_outcomes(self, actions):
+        """What the move phase of step(actions) would do to every agent (VecPogema.move_outcomes): per agent a dict
+        with `next_xy` (row, col), `outcome` (a name of pogema_amd.OUTCOMES) and `blocker` (an agent index or None)."""
+        from ._lib import OUTCOMES
+        next_xy, outcome, blocker, _ = (t[0].cpu().numpy() for t in
+                                        self._vec.move_outcomes(np.asarray(actions, dtype=np.int64)[None]))
+        return [{"next_xy": (int(next_xy[i, 0]), int(next_xy[i, 1])), "outcome": OUTCOMES[int(outcome[i])],
+                 "blocker": int(blocker[i]) if blocker[i] >= 0 else None} for i in range(outcome.shape[0])]
+
     def _metrics_dict(self, values):
         from ._lib import METRIC_NAMES
         metrics = {k: float(x) for k, x in zip(METRIC_NAMES, values)}

@@ -1,5 +1,5 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
-cooperative planner and its multi-step lookahead, collision shielding and direction-to-goal planes.  Each is one C-ABI
+cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes and move outcomes.  Each is one C-ABI
 call into caller-owned or fresh output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
 from __future__ import annotations
@@ -41,7 +41,7 @@ def _split(out, names):
 
 class QueryMixin:
     """The queries of a VecPogema.  Expects of the class it is mixed into: `_handle`, `_lib`, `device`, `batch`,
-    `num_agents`, `window`, `_ACTION_CODE`, `_stream()`."""
+    `num_agents`, `window`, `_ACTION_CODE`, `_prepare_actions()`, `_stream()`."""
 
     _SCORE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # PGX_SCORES_* of shield_actions' scores
 
@@ -255,3 +255,32 @@ class QueryMixin:
         _lib.check(self._lib.pgx_goal_directions(self._handle, 0, out.data_ptr(), _lib.DIRECTIONS_FORMATS[format],
                                                  self._stream()))
         return out
+
+    def move_outcomes(self, actions, out=None):
+        """Move outcomes (docs/SPEC.md S17): what the move phase of step(actions) would do to every agent and why a move
+        that fails does, under this env's collision system and `soft_vertex` rule -- computed on the device from the
+        current state, the state the next step() reads, which this call leaves untouched.  Returns
+            (next_xy int32 [batch, agents, 2]: the cell the agent stands on after the moves, unpadded (row, col), before
+                 goals, hiding, new lifelong targets and auto-reset; an inactive agent's own cell;
+             outcome uint8 [batch, agents]: an index into pogema_amd.OUTCOMES -- STAY (inactive, noop, out-of-range
+                 action), MOVED, OBSTACLE, SWAP, OCCUPIED (the agent on the destination stays), FOLLOW (it leaves, but
+                 the collision system forbids following: never under "soft"), CONTESTED (another mover claims the cell);
+             blocker int32 [batch, agents]: the agent standing on the destination for SWAP / OCCUPIED / FOLLOW, the
+                 lowest-index other claimant for CONTESTED, else -1;
+             counts int32 [batch, NUM_OUTCOMES]: the env's active agents per code).
+        `actions`: as step() takes them; a value outside 0..4 counts as 0 whatever Semantics.bad_action says, and the
+        call neither raises for it nor counts it.  One kernel launch: allocates nothing on the engine side,
+        stream-ordered, no host sync, capturable in a HIP graph from the first call.
+        `out=(next_xy, outcome, blocker, counts)`: caller-owned contiguous tensors of those dtypes and shapes on this
+        device."""
+        B, A = self.batch, self.num_agents
+        actions = self._prepare_actions(actions)
+        next_xy, outcome, blocker, counts = _split(out, ("next_xy", "outcome", "blocker", "counts"))
+        next_xy = query_output("out[next_xy]", next_xy, torch.int32, (B, A, 2), self.device)
+        outcome = query_output("out[outcome]", outcome, torch.uint8, (B, A), self.device)
+        blocker = query_output("out[blocker]", blocker, torch.int32, (B, A), self.device)
+        counts = query_output("out[counts]", counts, torch.int32, (B, _lib.NUM_OUTCOMES), self.device)
+        _lib.check(self._lib.pgx_move_outcomes(self._handle, actions.data_ptr(), self._ACTION_CODE[actions.dtype], 0,
+                                               next_xy.data_ptr(), outcome.data_ptr(), blocker.data_ptr(),
+                                               counts.data_ptr(), self._stream()))
+        return next_xy, outcome, blocker, counts
