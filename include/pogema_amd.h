@@ -558,6 +558,43 @@ int pgx_move_outcomes(pgx_env* env, const void* actions, int32_t action_dtype, i
 #define PGX_DIRECTIONS_BITS 2
 int pgx_goal_directions(pgx_env* env, int32_t flags, void* out, int32_t format, void* stream);
 
+/* Policy input (docs/SPEC.md S18): the stack of binary window planes a learnt MAPF policy reads, written once, in the
+ * order and the number format the network takes -- read from the current device state, the state the next pgx_step
+ * reads, which this call does not change.  Plane c of every agent's window is the channel channels[c]:
+ *   PGX_CHANNEL_OBSTACLES    plane 0 of pgx_observe, bit for bit (the border ring and random_outside included)
+ *   PGX_CHANNEL_AGENTS       plane 1 of pgx_observe, bit for bit (hidden agents absent, soft_occupancy honoured)
+ *   PGX_CHANNEL_TARGET       plane 2 of pgx_observe, bit for bit (the agent's target, clamped per axis to the window)
+ *   PGX_CHANNEL_OTHER_GOALS  1 at (r + clamp(fx_j - x, -r, r), r + clamp(fy_j - y, -r, r)) for the target (fx_j, fy_j)
+ *                            of every agent j that pgx_visible_agents calls visible to this agent at (x, y) -- another
+ *                            agent with bit 0 of is_active set, standing in the window -- however many there are; all
+ *                            zero for an agent that is not active itself
+ *   PGX_CHANNEL_UP, _DOWN, _LEFT, _RIGHT   planes 0..3 of pgx_goal_directions, bit for bit
+ * For an agent that is not active, the first three are what pgx_observe writes for it and the other five are zero.
+ *   channels      host array of num_channels distinct PGX_CHANNEL_* codes, read before the call returns
+ *   num_channels  1..PGX_NUM_CHANNELS
+ *   dtype         PGX_OBS_F32, PGX_OBS_U8, PGX_OBS_BF16 or PGX_OBS_F16: the elements of `out`, 0 / 1 in that format;
+ *                 chosen per call, whatever obs_dtype the handle was created with
+ *   out           device buffer [batch, agents, num_channels, 2r+1, 2r+1] of dtype, must not be NULL, aligned to its
+ *                 element size.  A 16-byte aligned `out` is written with 16-byte stores, any other with one store per
+ *                 element, which is markedly slower (a fresh device allocation is aligned).
+ * Without a direction channel the call is one launch that reads no distance field and allocates nothing: asynchronous
+ * on `stream`, no host sync, capturable in a HIP graph from the first call; pgx_cost_to_go_builds does not move.  With
+ * one it shares pgx_cost_to_go's cache exactly as pgx_goal_directions does: the stale fields are rebuilt (and counted)
+ * first, and whichever entry point uses the cache first allocates it -- inside a graph capture that first call returns
+ * PGX_E_STATE, a failed allocation PGX_E_NOMEM / PGX_E_HIP naming the bytes.  PGX_E_INVALID for a NULL `channels` or
+ * `out`, a count outside 1..PGX_NUM_CHANNELS, a code outside 0..7 or given twice, an unknown dtype or a misaligned `out`
+ * (checked before the handle: no device needed); PGX_E_STATE before the first reset, like pgx_step. */
+#define PGX_CHANNEL_OBSTACLES 0
+#define PGX_CHANNEL_AGENTS 1
+#define PGX_CHANNEL_TARGET 2
+#define PGX_CHANNEL_OTHER_GOALS 3
+#define PGX_CHANNEL_UP 4
+#define PGX_CHANNEL_DOWN 5
+#define PGX_CHANNEL_LEFT 6
+#define PGX_CHANNEL_RIGHT 7
+#define PGX_NUM_CHANNELS 8
+int pgx_policy_input(pgx_env* env, const int32_t* channels, int32_t num_channels, int32_t dtype, void* out, void* stream);
+
 /* Number of out-of-range actions (outside 0..4) that ACTIVE agents submitted since the last call (bad_action =
  * PGX_BAD_ACTION_FLAG only; otherwise always 0).  Inactive agents' actions are never looked at, as in the reference's
  * `if self.grid.is_active[agent_idx]` guards.  Synchronises `stream`, then clears the counter.  The host side turns a

@@ -62,6 +62,10 @@ PLAN_FIXED_PRIORITY = 1  # PGX_PLAN_FIXED_PRIORITY: flag of pgx_pibt_plan
 # PGX_OUTCOME_*: the codes of pgx_move_outcomes, index = code (docs/SPEC.md S17)
 OUTCOMES = ("STAY", "MOVED", "OBSTACLE", "SWAP", "OCCUPIED", "FOLLOW", "CONTESTED")
 NUM_OUTCOMES = len(OUTCOMES)  # PGX_NUM_OUTCOMES
+# PGX_CHANNEL_*: the planes of pgx_policy_input, name -> code (docs/SPEC.md S18); its dtype table is OBS_DTYPES (PGX_OBS_*)
+POLICY_CHANNELS = {"obstacles": 0, "agents": 1, "target": 2, "other_goals": 3, "up": 4, "down": 5, "left": 6, "right": 7}
+NUM_CHANNELS = len(POLICY_CHANNELS)  # PGX_NUM_CHANNELS
+DEFAULT_POLICY_CHANNELS = ("obstacles", "agents", "target", "up", "down", "left", "right")
 
 
 # every symbol include/pogema_amd.h declares; tests/test_abi.py checks the library exports them all
@@ -74,6 +78,7 @@ EXPORTED_SYMBOLS = (
     "pgx_expert_actions", "pgx_set_map_pool", "pgx_reset_pool", "pgx_regenerate_pool", "pgx_get_map_index",
     "pgx_cost_to_go", "pgx_cost_to_go_bytes", "pgx_cost_to_go_builds", "pgx_visible_agents", "pgx_pibt_actions",
     "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan", "pgx_move_outcomes",
+    "pgx_policy_input",
 )
 
 
@@ -201,6 +206,8 @@ def load() -> C.CDLL:
     lib.pgx_shield_actions.restype = C.c_int
     lib.pgx_move_outcomes.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.pgx_move_outcomes.restype = C.c_int
+    lib.pgx_policy_input.argtypes = [vp, C.POINTER(i32), i32, i32, vp, vp]
+    lib.pgx_policy_input.restype = C.c_int
     lib.pgx_set_map_pool.argtypes = [vp, vp, i32, vp, vp]
     lib.pgx_set_map_pool.restype = C.c_int
     lib.pgx_reset_pool.argtypes = [vp, u64, vp, i32, vp]

@@ -134,7 +134,7 @@ struct pgx_env {
     DevBuf<uint32_t> pool_cap;            // [M] start/target pairs each map can hold
     DevBuf<int32_t> map_index;            // [B] pool index of each env's map, -1 after a non-pool install
     // cost-to-go cache (docs/SPEC.md S11, pgx::cost_to_go_layout), allocated by the first pgx_cost_to_go,
-    // pgx_pibt_actions, pgx_pibt_plan or pgx_goal_directions
+    // pgx_pibt_actions, pgx_pibt_plan, pgx_goal_directions or pgx_policy_input with a direction channel
     DevBuf<uint8_t> c2g;
 };
 
@@ -1005,7 +1005,7 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
 
 // The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
 // first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_goal_directions,
-// pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE).  `who` names that entry point in the error messages.
+// pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE, pgx_policy_input with a direction channel).  `who` names that entry point in the error messages.
 static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p) {
     const pgx_config& c = e->cfg;
     const pgx::CostToGoLayout l = pgx::cost_to_go_layout(c.batch, c.num_agents, c.height, c.width);
@@ -1208,6 +1208,51 @@ int pgx_goal_directions(pgx_env* e, int32_t flags, void* out, int32_t format, vo
     pgx::CostToGoParams p{};
     if (const int rc = cost_to_go_cache(e, s, who, &p)) return rc;
     PGX_HIP(pgx::launch_goal_directions(p, out, format, s));
+    return PGX_OK;
+}
+
+// ---- policy input (docs/SPEC.md S18) ------------------------------------------------------------------------
+int pgx_policy_input(pgx_env* e, const int32_t* channels, int32_t num_channels, int32_t dtype, void* out, void* stream) {
+    static const char who[] = "pgx_policy_input";
+    // the argument checks come first and need no device
+    if (!out) return fail_msg(PGX_E_INVALID, "%s: out is null", who);
+    if (!channels) return fail_msg(PGX_E_INVALID, "%s: channels is null", who);
+    if (num_channels < 1 || num_channels > PGX_NUM_CHANNELS)
+        return fail_msg(PGX_E_INVALID, "%s: num_channels %d is outside 1..%d", who, num_channels, PGX_NUM_CHANNELS);
+    static_assert(PGX_NUM_CHANNELS == pgx::POLICY_CHANNELS && PGX_CHANNEL_OBSTACLES == 0 && PGX_CHANNEL_AGENTS == 1 &&
+                      PGX_CHANNEL_TARGET == 2 && PGX_CHANNEL_OTHER_GOALS == 3 && PGX_CHANNEL_UP == 4 && PGX_CHANNEL_DOWN == 5 &&
+                      PGX_CHANNEL_LEFT == 6 && PGX_CHANNEL_RIGHT == 7, "channel code k is bit k of the kernel's cell bytes");
+    uint32_t codes = 0, need = 0;
+    for (int c = 0; c < num_channels; ++c) {
+        const int32_t k = channels[c];
+        if (k < 0 || k >= PGX_NUM_CHANNELS)
+            return fail_msg(PGX_E_INVALID, "%s: channels[%d] = %d is outside 0..%d", who, c, k, PGX_NUM_CHANNELS - 1);
+        if (need & (1u << k)) return fail_msg(PGX_E_INVALID, "%s: channels[%d] = %d is given twice", who, c, k);
+        need |= 1u << k;
+        codes |= (uint32_t)k << (4 * c);
+    }
+    static_assert(PGX_OBS_F32 == pgx::POLICY_INPUT_F32 && PGX_OBS_U8 == pgx::POLICY_INPUT_U8 &&
+                      PGX_OBS_BF16 == pgx::POLICY_INPUT_BF16 && PGX_OBS_F16 == pgx::POLICY_INPUT_F16,
+                  "the kernel's dtype codes are the header's");
+    if (dtype != PGX_OBS_F32 && dtype != PGX_OBS_U8 && dtype != PGX_OBS_BF16 && dtype != PGX_OBS_F16)
+        return fail_msg(PGX_E_INVALID, "%s: bad dtype %d", who, dtype);
+    if (const int rc = check_aligned(who, "out", out, (size_t)obs_elem_bytes(dtype))) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::PolicyInputParams p{};
+    if (need & 0xF0u) {
+        if (const int rc = cost_to_go_cache(e, s, who, &p)) return rc;  // (fills the CostToGoParams base of p)
+    } else {
+        static_cast<pgx::StateView&>(p) = state_view(e);   // no cache, no allocation: one launch
+    }
+    p.num_channels = num_channels;
+    p.dtype = dtype;
+    p.codes = codes;
+    p.need = need;
+    p.one = dtype == PGX_OBS_F32 ? 0x3F800000u : dtype == PGX_OBS_BF16 ? 0x3F80u : dtype == PGX_OBS_F16 ? 0x3C00u : 1u;
+    p.planes = out;
+    PGX_HIP(pgx::launch_policy_input(p, s));
     return PGX_OK;
 }
 

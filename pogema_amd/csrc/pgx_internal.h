@@ -322,6 +322,21 @@ enum { DIRECTIONS_F32 = 0, DIRECTIONS_U8 = 1, DIRECTIONS_BITS = 2 };  // PGX_DIR
 // [B][A][4][2r+1][2r+1] float32 or u8, or [B][A][2r+1][2r+1] u8 masks
 hipError_t launch_goal_directions(const CostToGoParams& p, void* out, int format, hipStream_t stream);
 
+// ---- policy input (pgx_policy_input.hip): the network's window planes, chosen, ordered and typed per call ------------
+enum { POLICY_INPUT_F32 = 0, POLICY_INPUT_U8 = 1, POLICY_INPUT_BF16 = 2, POLICY_INPUT_F16 = 3 };  // PGX_OBS_* (include/pogema_amd.h)
+enum { POLICY_CHANNELS = 8 };                                                                     // PGX_NUM_CHANNELS
+struct PolicyInputParams : CostToGoParams {   // without a direction channel only the StateView part is used
+    int32_t num_channels;    // C, 1..POLICY_CHANNELS
+    int32_t dtype;           // POLICY_INPUT_*
+    uint32_t codes;          // the channel list: PGX_CHANNEL_* of output plane c in bits 4c .. 4c+3
+    uint32_t need;           // bit k set: channel code k is in the list
+    uint32_t one;            // the bit pattern of 1 in `dtype`
+    void* planes;            // [B][A][C][2r+1][2r+1] of `dtype`
+};
+// with a direction channel (need & 0xF0): the refresh of the cost-to-go cache `p` describes, then the planes; without
+// one: the planes alone, in one launch that reads no field
+hipError_t launch_policy_input(const PolicyInputParams& p, hipStream_t stream);
+
 // ---- neighbour lists (pgx_neighbours.hip) ---------------------------------------------------------------
 // (not derived from StateView: the kernel reads four of its fields, and this block of 56 bytes is fetched with two loads)
 struct NeighbourParams {

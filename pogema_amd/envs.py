@@ -16,6 +16,7 @@ from typing import Optional
 
 import numpy as np
 
+from ._lib import DEFAULT_POLICY_CHANNELS as _DEFAULT_POLICY_CHANNELS
 from .grid_config import GridConfig
 from .vec_env import VecPogema
 
@@ -189,6 +190,13 @@ class Pogema:
         arrays."""
         d = self._vec.goal_directions(format="uint8")[0].cpu().numpy()
         return [d[i] for i in range(d.shape[0])]
+
+    def policy_input(self, channels=_DEFAULT_POLICY_CHANNELS):
+        """The network's input planes of every agent (VecPogema.policy_input) as a list of uint8 (C, W, W) numpy
+        arrays, plane c the channel channels[c]."""
+        import torch
+        x = self._vec.policy_input(channels=channels, dtype=torch.uint8)[0].cpu().numpy()
+        return [x[i] for i in range(x.shape[0])]
 
     def visible_agents(self, k: int = 13):
         """The agents each agent sees in its window (VecPogema.visible_agents): per agent a list of (j, dx, dy) tuples,

@@ -1,5 +1,6 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
-cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes and move outcomes.  Each is one C-ABI
+cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes, move outcomes and the
+policy input.  Each is one C-ABI
 call into caller-owned or fresh output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
 from __future__ import annotations
@@ -37,6 +38,27 @@ def _split(out, names):
         if t is None:  # (None would read as "allocate one": the caller gives every output or none)
             raise ValueError(f"out[{name}] is None: out must be ({', '.join(names)}), every one a tensor")
     return tuple(out)
+
+
+def parse_channels(channels=_lib.DEFAULT_POLICY_CHANNELS):
+    """The channel list of policy_input() as a tuple of PGX_CHANNEL_* codes, in the caller's order; the default is the
+    seven-plane input: the observation, then the four direction planes.  Anything but a sequence of 1..8 distinct names of
+    _lib.POLICY_CHANNELS is a ValueError that names the offending entry and lists the vocabulary.  Needs no engine and
+    no GPU."""
+    table = _lib.POLICY_CHANNELS
+    known = f"the channels are {', '.join(repr(n) for n in table)}"
+    if isinstance(channels, (str, bytes)) or not isinstance(channels, (tuple, list)):
+        raise ValueError(f"channels must be a tuple or list of 1..{_lib.NUM_CHANNELS} channel names, got {channels!r}; {known}")
+    if not 1 <= len(channels) <= _lib.NUM_CHANNELS:
+        raise ValueError(f"channels must hold 1..{_lib.NUM_CHANNELS} names, got {len(channels)}; {known}")
+    codes = []
+    for k, name in enumerate(channels):
+        if not isinstance(name, str) or name not in table:
+            raise ValueError(f"channels[{k}] = {name!r} is not a channel; {known}")
+        if table[name] in codes:
+            raise ValueError(f"channels[{k}] = {name!r} is given twice; {known}")
+        codes.append(table[name])
+    return tuple(codes)
 
 
 class QueryMixin:
@@ -284,3 +306,29 @@ class QueryMixin:
                                                next_xy.data_ptr(), outcome.data_ptr(), blocker.data_ptr(),
                                                counts.data_ptr(), self._stream()))
         return next_xy, outcome, blocker, counts
+
+    def policy_input(self, channels=_lib.DEFAULT_POLICY_CHANNELS, dtype=torch.float32, out=None) -> torch.Tensor:
+        """The network's input tensor (docs/SPEC.md S18): [batch, agents, C, W, W] of 0 / 1 in `dtype`, plane c the
+        channel channels[c], written once in one launch -- computed on the device from the current state, the state
+        the next step() reads, which this call leaves untouched.
+        `channels`: a tuple or list of 1..8 distinct names, in the order the network wants them:
+            "obstacles", "agents", "target"  -- planes 0, 1, 2 of observe(), bit for bit;
+            "other_goals"  -- 1 where an agent visible_agents() calls visible has its target, clamped per axis to the
+                window's edge as "target" is; every visible agent counts, however many; all zero for an inactive agent;
+            "up", "down", "left", "right"  -- planes 0..3 of goal_directions(), bit for bit.
+        The default is ("obstacles", "agents", "target", "up", "down", "left", "right"), what
+        torch.cat((observe(), goal_directions()), 2) builds on a float32 engine.  PRIMAL reads the first four names,
+        SCRIMP all eight.
+        `dtype`: torch.float32, float16, bfloat16 or uint8, chosen per call whatever `obs_dtype` the engine has.
+        Without a direction channel: one launch that reads no distance field and allocates nothing, stream-ordered, no
+        host sync, capturable in a HIP graph from the first call.  With one it shares cost_to_go()'s cache under
+        goal_directions()' rules (stale fields are rebuilt first; whichever call is first allocates the cache, not inside
+        a graph capture).  `out`: a caller-owned contiguous tensor of that shape and dtype on this device."""
+        codes = parse_channels(channels)
+        if dtype not in _lib.OBS_DTYPES:
+            raise ValueError(f"dtype must be one of torch.float32, torch.float16, torch.bfloat16, torch.uint8, got {dtype!r}")
+        shape = (self.batch, self.num_agents, len(codes), self.window, self.window)
+        out = query_output("out", out, dtype, shape, self.device)
+        _lib.check(self._lib.pgx_policy_input(self._handle, (_lib.C.c_int32 * len(codes))(*codes), len(codes),
+                                              _lib.OBS_DTYPES[dtype], out.data_ptr(), self._stream()))
+        return out
