@@ -4,9 +4,12 @@ overridden: every lane layout, both tie-break modes, every priority form, score 
 steps of every collision system and on_target mode, in a crowd whose pushes fail, with a map pool and after
 set_targets.  Under `soft` every planned agent arrives on its next cell whatever the scores.  The default mode allocates
 nothing and is captured in a HIP graph as the first call ever made; tie_break="distance" shares cost_to_go()'s cache."""
+import contextlib
+
 import numpy as np
 import pytest
 
+from agent_counts import shared_fields
 from pibt_reference import check_invariants
 from shield_inputs import crowd_scores, crowd_state, random_scores, special_scores
 from shield_reference import shield_reference
@@ -30,9 +33,11 @@ def _check(env, scores, priority=None, tie_break=None, what="", invariants=False
     assert overridden.dtype == torch.uint8 and tuple(overridden.shape) == (B, A)
     st = env.get_state()
     maps = installed_maps(env)
-    pos, active = st["agents_xy"].cpu().numpy(), st["is_active"].cpu().numpy()
-    ref = shield_reference(maps, pos, st["targets_xy"].cpu().numpy(), active, scores.float().cpu().numpy(),
-                           None if priority is None else priority.cpu().numpy(), tie_break)
+    pos, active, tgt = st["agents_xy"].cpu().numpy(), st["is_active"].cpu().numpy(), st["targets_xy"].cpu().numpy()
+    # (above 256 agents the reference's one search per distinct target and call comes from a shared memo)
+    with shared_fields(maps, tgt) if A > 256 and tie_break is not None else contextlib.nullcontext():
+        ref = shield_reference(maps, pos, tgt, active, scores.float().cpu().numpy(),
+                               None if priority is None else priority.cpu().numpy(), tie_break)
     for name, g, w in (("actions", actions.cpu().numpy(), ref[0]), ("next_xy", next_xy.cpu().numpy(), ref[1]),
                        ("overridden", overridden.cpu().numpy(), ref[2])):
         bad = np.argwhere(g != w)

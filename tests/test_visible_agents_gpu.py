@@ -5,6 +5,7 @@ engine's own observation.  The call leaves the engine state alone and can be cap
 import numpy as np
 import pytest
 
+from agent_counts import LAYOUT_ROWS, radii_accepted
 from visible_agents_reference import visible_agents_reference
 from util import lazy_torch, mixed_actions
 
@@ -33,17 +34,21 @@ def _check(env, k, what="", full=None):
 KS = (1, 5, 8, 13, 16, 17, 32)
 
 # (agents, map side, batch): one row per lane layout -- several envs per wave, one wave, several waves, several workgroups
-# per env -- with batches that leave the last workgroup partly filled.  Every row runs obs_radius 1, 5 and 15 but the last:
-# the engine itself refuses 1024 agents with a 31 x 31 window (README.md "Limits": the step kernel's LDS budget).
+# per env -- with batches that leave the last workgroup partly filled.  Every row runs those of obs_radius 1, 5 and 15 the
+# engine admits: it refuses 512 agents and more with a 31 x 31 window (README.md "Limits": the step kernel's LDS budget).
+# The rows between 256 and 1024 agents are tests/agent_counts.py's: 3, 2 and 1 envs per 1024-lane workgroup of the planners
+# and the outcomes, a last workgroup that is partly filled, ragged last chunks of the neighbour lists (1, 86 and 255 rows).
 LAYOUTS = [(1, 6, 300), (2, 6, 131), (3, 7, 90), (8, 10, 70), (16, 12, 37), (33, 14, 9), (64, 16, 7), (65, 18, 5),
-           (200, 28, 3), (1024, 64, 2)]
+           (200, 28, 3), *LAYOUT_ROWS, (1024, 64, 2)]
 
 
 @pytest.mark.parametrize("agents,size,batch", LAYOUTS)
 def test_every_lane_layout_matches_reference(agents, size, batch):
     from pogema_amd import GridConfig, VecPogema
     rng = np.random.default_rng(agents)
-    for r in ((1, 5, 15) if agents < 1024 else (1, 5)):
+    radii = radii_accepted(agents, size, batch)
+    assert radii == (1, 5, 15) or (agents >= 512 and radii == (1, 5))
+    for r in radii:
         gc = GridConfig(size=size, num_agents=agents, obs_radius=r, density=0.1, seed=agents + r,
                         collision_system="soft", on_target="finish", max_episode_steps=64)
         env = VecPogema(gc, batch=batch)
