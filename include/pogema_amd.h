@@ -250,6 +250,22 @@ int pgx_get_map(pgx_env* env, uint8_t* obstacles, void* stream);
 int pgx_step(pgx_env* env, const void* actions, int action_dtype, void* obs, float* rewards,
              uint8_t* terminated, uint8_t* truncated, uint8_t* is_active, void* stream);
 
+/* pgx_step for an output set that the caller KEEPS between calls: the same step, the same five outputs, but the launch
+ * may leave out stores of target-plane zeros that `obs` still holds from the previous pgx_step_held call that wrote it.
+ *   held      device u8 [batch, agents], one per `obs` buffer, owned by the caller together with it: the flat window index
+ *             (row * (2r+1) + col) of the 1.0 that the last pgx_step_held left in each agent's target plane of `obs`;
+ *             255 = unknown.  Read and rewritten by the call.
+ *   refresh   != 0: nothing is assumed about `obs` -- every byte is written, `held` is recorded.  Pass it whenever
+ *             anything but pgx_step_held with this `held` may have written `obs` since (or `held` is not initialised).
+ * With refresh == 0 the result is the one of pgx_step provided `obs` holds exactly what the previous call with this
+ * `held` left in it.  Exists for float32 observations with obs_radius <= 7 outside the large-map layout
+ * (pgx_held_available); for any other configuration, and with obs == NULL or held == NULL, this IS pgx_step.
+ * Like pgx_step it only enqueues one launch (the kernel is configured at pgx_create) and can be captured in a HIP graph. */
+int pgx_step_held(pgx_env* env, const void* actions, int action_dtype, void* obs, uint8_t* held, int32_t refresh,
+                  float* rewards, uint8_t* terminated, uint8_t* truncated, uint8_t* is_active, void* stream);
+/* 1 when pgx_step_held has a kernel of its own for this handle's configuration, 0 when it runs pgx_step */
+int pgx_held_available(const pgx_env* env);
+
 /* How pgx_step's workgroups (one per environment, or per group of small environments) are shared out over the 8 XCDs:
  * shares[x] of them run on XCD x (host pointer, 8 entries).  Equal by default.  The XCDs do not get through their
  * observation streams equally fast (the odd ones lag 5-15 %), and with equal shares the fast ones

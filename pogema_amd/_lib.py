@@ -71,7 +71,7 @@ DEFAULT_POLICY_CHANNELS = ("obstacles", "agents", "target", "up", "down", "left"
 # every symbol include/pogema_amd.h declares; tests/test_abi.py checks the library exports them all
 EXPORTED_SYMBOLS = (
     "pgx_abi_version", "pgx_last_error", "pgx_create", "pgx_check_config", "pgx_destroy", "pgx_obs_elems", "pgx_agent_elems",
-    "pgx_reset_from_state", "pgx_reset_random", "pgx_regenerate", "pgx_regenerate_failures", "pgx_get_map", "pgx_step", "pgx_observe", "pgx_set_metrics_buffers", "pgx_get_state", "pgx_generate", "pgx_place_agents",
+    "pgx_reset_from_state", "pgx_reset_random", "pgx_regenerate", "pgx_regenerate_failures", "pgx_get_map", "pgx_step", "pgx_step_held", "pgx_held_available", "pgx_observe", "pgx_set_metrics_buffers", "pgx_get_state", "pgx_generate", "pgx_place_agents",
     "pgx_snapshot_bytes", "pgx_save_snapshot", "pgx_load_snapshot", "pgx_time_observe", "pgx_bad_action_count",
     "pgx_buffers_create", "pgx_buffers_ptr", "pgx_buffers_get_info", "pgx_buffers_destroy", "pgx_set_targets",
     "pgx_np_streams", "pgx_np_streams_host", "pgx_np_generate", "pgx_np_generate_host", "pgx_rollout", "pgx_buffers_stride", "pgx_buffers_drop", "pgx_xcd_shares", "pgx_xcd_tune", "pgx_buffers_create_at", "pgx_time_observe_pair", "pgx_buffers_va_reserved", "pgx_get_geometry",
@@ -230,6 +230,9 @@ def load() -> C.CDLL:
     lib.pgx_load_snapshot.argtypes = [vp, vp, vp]
     lib.pgx_save_snapshot.restype = lib.pgx_load_snapshot.restype = C.c_int
     lib.pgx_step.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.pgx_step_held.argtypes = [vp, vp, C.c_int, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.pgx_held_available.argtypes = [vp]
+    lib.pgx_step_held.restype = lib.pgx_held_available.restype = C.c_int
     lib.pgx_observe.argtypes = [vp, vp, vp]
     lib.pgx_set_metrics_buffers.argtypes = [vp, vp, vp]
     lib.pgx_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]

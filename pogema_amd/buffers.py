@@ -420,7 +420,16 @@ class RecyclingOutputs:
     "Nobody references it" is read off the storages' reference counts (torch._C._storage_Use_Count, 0.15 us each); a
     handed-out tensor is `master.detach()` (1 us) -- together half the host time of five torch.empty calls.  The hook is
     private torch API: `storage_count_hook()` verifies its meaning before it is used, `available()` says whether it
-    passed; without it the caller allocates fresh tensors (and has been warned)."""
+    passed; without it the caller allocates fresh tensors (and has been warned).
+
+    Held zeros (pgx_step_held): every set also owns `held`, uint8 [batch, agents] -- where the engine's last held write left
+    the 1.0 of each agent's target plane, 255 = unknown -- and remembers the observation master's `_version` after that
+    write.  `take_for_step()` says whether the set is still TRUSTED to hold exactly what that write left: its version is the
+    recorded one.  THE CONTRACT: `detach()` and views share the master's version counter, so every torch in-place operation
+    through any alias of a handed-out tensor makes the set untrusted (the next held step rewrites everything).  Writes
+    that torch does not see -- through `.data`, DLPack / `__cuda_array_interface__` consumers, kernels given `data_ptr()`
+    -- do NOT, and are not allowed on a returned observation tensor while the feature is on (VecPogema(held_zeros=False) /
+    PGX_HELD_ZEROS=0 switch it off).  Plain `take()` forgets the record: whoever gets the set that way may write it."""
 
     @staticmethod
     def available() -> bool:
@@ -444,6 +453,8 @@ class RecyclingOutputs:
             self._sets.append((members, storages, tuple(st._cdata for st in storages)))
         del obs, block, members, storages
         self._idle = [tuple(self._count(c) for c in cdata) for _, _, cdata in self._sets]
+        self._held = [torch.full((batch, agents), 255, dtype=torch.uint8, device=dev) for _ in self._sets]
+        self._vouched = [None] * len(self._sets)  # the observation master's _version after the engine's last held write
         self._next = 0
         self.taken = 0      # statistics: sets handed out / requests that found every set in use
         self.misses = 0
@@ -470,19 +481,59 @@ class RecyclingOutputs:
         for i in reversed(idle):
             del self._sets[i]
             del self._idle[i]
+            del self._held[i]
+            del self._vouched[i]
         self._next = 0
         return out
 
-    def take(self, with_obs: bool = True):
-        """(obs, rewards, terminated, truncated, is_active) of an unreferenced set -- least recently handed out first --
-        or None.  with_obs=False: obs is None (the set's observation buffer stays idle)."""
+    def _take_index(self):
         n = len(self._sets)
         for k in range(n):
             i = (self._next + k) % n
             if self._is_idle(i):
                 self._next = (i + 1) % n
                 self.taken += 1
-                m = self._sets[i][0]
-                return (m[0].detach() if with_obs else None, m[1].detach(), m[2].detach(), m[3].detach(), m[4].detach())
+                return i
         self.misses += 1
         return None
+
+    def _hand_out(self, i: int, with_obs: bool):
+        m = self._sets[i][0]
+        return (m[0].detach() if with_obs else None, m[1].detach(), m[2].detach(), m[3].detach(), m[4].detach())
+
+    @staticmethod
+    def _version(t):
+        try:
+            return t._version
+        except Exception:  # noqa: BLE001  (inference tensors have no version counter: never trusted)
+            return None
+
+    def take(self, with_obs: bool = True):
+        """(obs, rewards, terminated, truncated, is_active) of an unreferenced set -- least recently handed out first --
+        or None.  with_obs=False: obs is None (the set's observation buffer stays idle).  Whoever takes the observation
+        buffer this way may write it with anything: the set's held-zeros record is forgotten."""
+        i = self._take_index()
+        if i is None:
+            return None
+        if with_obs:
+            self._vouched[i] = None
+        return self._hand_out(i, with_obs)
+
+    def take_for_step(self, with_obs: bool = True):
+        """take() for a step that writes the observation with pgx_step_held: -> (outputs, held, trusted, index) or None.
+        `trusted`: the buffer still holds exactly what the engine's last held write left in it (that write was vouched for
+        and no torch operation has written through any alias since).  The record is dropped here; `vouch(index)` after the
+        launch sets it again."""
+        i = self._take_index()
+        if i is None:
+            return None
+        trusted = False
+        if with_obs:
+            v = self._vouched[i]
+            trusted = v is not None and self._version(self._sets[i][0][0]) == v
+            self._vouched[i] = None
+        return self._hand_out(i, with_obs), self._held[i], trusted, i
+
+    def vouch(self, i: int):
+        """The engine has just written set i's observation with pgx_step_held (`held` records it)."""
+        self._vouched[i] = self._version(self._sets[i][0][0])

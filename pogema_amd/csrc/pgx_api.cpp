@@ -420,6 +420,8 @@ static int create_device_side(pgx_env* e) {
         err = pgx::launch_init_np_lifelong(e->np_state0, cfg->seed, cfg->env_index_base, cfg->batch, A, nullptr);
     if (err == hipSuccess && e->np_state0) err = hipStreamSynchronize(nullptr);
     if (err == hipSuccess) err = pgx::prepare_step(e->geo, e->geo_roll);
+    if (err == hipSuccess && pgx::held_available(e->geo, A, e->W, obs_elem_bytes(cfg->obs_dtype)))
+        err = pgx::prepare_step_held(e->geo, A, e->W);  // here, not at the first pgx_step_held: the call stays capturable
     if (err != hipSuccess)
         return fail_msg(PGX_E_HIP, "cannot configure the step kernel (%zu bytes of LDS): %s", e->geo.lds_bytes,
                         hipGetErrorString(err));
@@ -920,6 +922,33 @@ int pgx_step(pgx_env* e, const void* actions, int action_dtype, void* obs, float
     p.truncated = truncated;
     p.act_out = is_active;
     PGX_HIP(pgx::launch_step(p, e->geo, (hipStream_t)stream));
+    return PGX_OK;
+}
+
+int pgx_held_available(const pgx_env* e) {
+    if (!e) return 0;
+    return pgx::held_available(e->geo, e->cfg.num_agents, e->W, obs_elem_bytes(e->cfg.obs_dtype)) ? 1 : 0;
+}
+
+int pgx_step_held(pgx_env* e, const void* actions, int action_dtype, void* obs, uint8_t* held, int32_t refresh, float* rewards,
+                  uint8_t* terminated, uint8_t* truncated, uint8_t* is_active, void* stream) {
+    // no held instance for this shape, or nothing to hold: the plain step
+    if (!e || !obs || !held || !pgx_held_available(e))
+        return pgx_step(e, actions, action_dtype, obs, rewards, terminated, truncated, is_active, stream);
+    if (!actions || !rewards || !terminated || !truncated) return fail_msg(PGX_E_INVALID, "pgx_step_held: null argument");
+    if (const int rc = check_action_dtype("pgx_step_held", action_dtype)) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, "pgx_step_held", true)) return rc;
+    pgx::StepParams p = step_params(e, e->geo);
+    p.mode = pgx::MODE_STEP;
+    p.action_dtype = action_dtype;
+    p.actions = actions;
+    p.obs = static_cast<float*>(obs);
+    p.rewards = rewards;
+    p.terminated = terminated;
+    p.truncated = truncated;
+    p.act_out = is_active;
+    PGX_HIP(pgx::launch_step_held(p, e->geo, held, refresh != 0, (hipStream_t)stream));
     return PGX_OK;
 }
 

@@ -155,6 +155,14 @@ struct StepParams {
     unsigned long long* dbg;  // diagnostic (PGX_FLAGS bit2): per-workgroup {start, resolve done, first store, end} clocks
 };
 
+// step_held (pgx_step_held): what the output set still holds, the kernel's second argument
+struct HeldParams {
+    uint8_t* held;     // [B][A]  flat window index of the 1.0 in the agent's target plane of `obs` (255: unknown); read and rewritten
+    int32_t refresh;   // 1: `obs` is not vouched for -- write everything, record the indices
+    int32_t lds_word;  // where the skip bitmap starts in LDS (32-bit words; behind the step kernel's own layout)
+    int32_t words;     // its size
+};
+
 // pgx_rollout: what changes from one step of the launch to the next
 struct RolloutParams {
     int32_t steps;
@@ -195,6 +203,11 @@ hipError_t prepare_step(const StepGeometry& g, const StepGeometry& roll);
 // the function, shared by every live handle; pgx_kernels.hip)
 hipError_t raise_lds_limit(const void* fn, size_t lds_bytes);
 hipError_t launch_step(const StepParams& p, const StepGeometry& g, hipStream_t stream);
+// the held form of launch_step (pgx_kernels.hip: step_held): whether launch shape `g` has one, its LDS opt-in (once per
+// handle), the launch
+bool held_available(const StepGeometry& g, int A, int W, int obs_elem_bytes);
+hipError_t prepare_step_held(const StepGeometry& g, int A, int W);
+hipError_t launch_step_held(const StepParams& p, const StepGeometry& g, uint8_t* held, bool refresh, hipStream_t stream);
 // splits `blocks` workgroups over the XCDs by `w`; returns the grid size (8 * the largest share)
 int xcd_partition(int blocks, const float w[8], int32_t n[8], int32_t base[8]);
 hipError_t launch_rollout(const StepParams& p, const RolloutParams& rp, const StepGeometry& g, hipStream_t stream);

@@ -301,16 +301,27 @@ __device__ __forceinline__ void stream_obs_h16(uint16_t* out, size_t base, int n
 // store_obs16's policy is a compile-time constant here: with the switch inside the loop every 16-byte store dragged ~25
 // scalar instructions and branches along -- configs[1] 8.3 -> 7.7 us, configs[2] 116.3 -> 115.2, configs[3] 38.75 -> 38.5,
 // configs[4] 421.3 -> 419.0 (in-process A/B on shared buffers, profiles/r3/stream_loop_ab.txt)
-template <int POLICY, bool PIPE>
+// HELD (step_held): `skip` is a bitmap over the slice's aligned 2^PGX_HELD_UNIT_LOG2-byte units -- a set bit: the unit lies
+// inside one agent's target plane and holds zeros in the buffer already (step_body, in front of the rows' barrier) -- and float4 q
+// lies in unit (q + a0) >> (PGX_HELD_UNIT_LOG2 - 4).  All 16-byte stores of a unit take the same decision; the word of the
+// next iteration is read with that iteration's rows.
+#ifndef PGX_HELD_UNIT_LOG2
+#define PGX_HELD_UNIT_LOG2 7
+#endif
+template <int POLICY, bool PIPE, bool HELD = false>
 __device__ __forceinline__ void stream_rows16_loop(f32x4_t* out4, const uint32_t* rows32, int W, int row, int col, int q0, int q1,
-                                                   int qs, int last_word) {
+                                                   int qs, int last_word, [[maybe_unused]] const uint32_t* skip = nullptr,
+                                                   [[maybe_unused]] int a0 = 0, [[maybe_unused]] int last_skip = 0) {
     const int drow = (4 * qs) / W, dcol = 4 * qs - drow * W;
+    static_assert(!HELD || PIPE, "the held stream exists in the pipelined form only");
     if constexpr (PIPE) {
         // software pipeline: the row words of iteration k+1 are read from LDS while iteration k is converted and stored
         // (the compiler does not do it: one exposed LDS round trip per 1-KiB store otherwise; configs[2] 113.8 -> 112.9 us,
         // profiles/r3/stream_loop_ab.txt); the read past the last iteration is clamped to the zero pad behind the rows
         const int fw = min(row >> 1, last_word);  // (a lane with q0 >= q1 starts beyond the rows: clamped like the in-loop read)
         uint32_t w0 = rows32[fw], w1 = rows32[fw + 1];
+        [[maybe_unused]] uint32_t sw = 0u;  // HELD: the skip word of this iteration's unit
+        if constexpr (HELD) sw = skip[min((q0 + a0) >> (PGX_HELD_UNIT_LOG2 + 1), last_skip)];
         for (int q = q0; q < q1; q += qs) {
             int ncol = col + dcol, nrow = row + drow;
             if (ncol >= W) {
@@ -319,16 +330,23 @@ __device__ __forceinline__ void stream_rows16_loop(f32x4_t* out4, const uint32_t
             }
             const int nw = min(nrow >> 1, last_word);
             const uint32_t n0 = rows32[nw], n1 = rows32[nw + 1];
-            const uint32_t pair = (uint32_t)((((uint64_t)w1 << 32) | w0) >> (16 * (row & 1)));  // row | row+1 << 16
-            const uint32_t b = ((pair & 0xFFFFu) >> col) | ((pair >> 16) << (W - col));
-            f32x4_t v;
-            v.x = (float)(b & 1u);
-            v.y = (float)((b >> 1) & 1u);
-            v.z = (float)((b >> 2) & 1u);
-            v.w = (float)((b >> 3) & 1u);
-            store_obs16(&out4[q], v, (uint32_t)POLICY);
+            [[maybe_unused]] uint32_t nsw = 0u;
+            if constexpr (HELD) nsw = skip[min((q + qs + a0) >> (PGX_HELD_UNIT_LOG2 + 1), last_skip)];
+            bool write = true;
+            if constexpr (HELD) write = !((sw >> (((q + a0) >> (PGX_HELD_UNIT_LOG2 - 4)) & 31)) & 1u);
+            if (write) {
+                const uint32_t pair = (uint32_t)((((uint64_t)w1 << 32) | w0) >> (16 * (row & 1)));  // row | row+1 << 16
+                const uint32_t b = ((pair & 0xFFFFu) >> col) | ((pair >> 16) << (W - col));
+                f32x4_t v;
+                v.x = (float)(b & 1u);
+                v.y = (float)((b >> 1) & 1u);
+                v.z = (float)((b >> 2) & 1u);
+                v.w = (float)((b >> 3) & 1u);
+                store_obs16(&out4[q], v, (uint32_t)POLICY);
+            }
             w0 = n0;
             w1 = n1;
+            if constexpr (HELD) sw = nsw;
             row = nrow;
             col = ncol;
         }
@@ -378,15 +396,23 @@ __device__ __forceinline__ void stream_rows16_loop_h16(f32x4_t* out4, const uint
     }
 }
 
-template <bool PIPE>
+template <bool PIPE, bool HELD = false>
 __device__ __forceinline__ void stream_rows16_span(f32x4_t* out4, const uint32_t* rows32, int head, int W, uint32_t magic,
-                                                   uint32_t spol, int q0, int q1, int qs, int last_word) {
+                                                   uint32_t spol, int q0, int q1, int qs, int last_word,
+                                                   [[maybe_unused]] const uint32_t* skip = nullptr, [[maybe_unused]] int a0 = 0,
+                                                   [[maybe_unused]] int last_skip = 0) {
     const int e0 = head + (q0 << 2);
     const int row = (int)__umulhi((uint32_t)e0, magic);
     const int col = e0 - row * W;
+    if constexpr (HELD) {
+        if (spol == 0u) stream_rows16_loop<0, PIPE, true>(out4, rows32, W, row, col, q0, q1, qs, last_word, skip, a0, last_skip);
+        else if (spol == 1u) stream_rows16_loop<1, PIPE, true>(out4, rows32, W, row, col, q0, q1, qs, last_word, skip, a0, last_skip);
+        else stream_rows16_loop<2, PIPE, true>(out4, rows32, W, row, col, q0, q1, qs, last_word, skip, a0, last_skip);
+    } else {
     if (spol == 0u) stream_rows16_loop<0, PIPE>(out4, rows32, W, row, col, q0, q1, qs, last_word);
     else if (spol == 1u) stream_rows16_loop<1, PIPE>(out4, rows32, W, row, col, q0, q1, qs, last_word);
     else stream_rows16_loop<2, PIPE>(out4, rows32, W, row, col, q0, q1, qs, last_word);
+    }
 }
 __device__ __forceinline__ void stream_rows16_edges(float* out, const uint16_t* rows16, int n, int head, int tail0, int W,
                                                     uint32_t magic, int t8) {
@@ -449,9 +475,14 @@ __device__ __forceinline__ uint32_t pack_action4(int a) { return (uint32_t)a <= 
 //                 per configs[1] step one after the other (profiles/r6/rollout_timeline_after.txt); the pair overlaps
 //                 them, and the streamer's bursts follow each other without the resolver's pause in between
 //                 (tools/drift_probe2.hip: what an HBM-sized configs[3] ring loses).
-template <int G, bool MW, bool P16, bool ROLL, bool BIG, bool PC, typename P, typename R>
-__device__ __forceinline__ void step_body(P& p, R& rp, const int t, const int slot, Carry& c) {
+//   HELD        : step_held only (float32, P16, one step per launch): the launch may leave out stores of target-plane zeros
+//                 that the output buffer still holds from this kernel's previous write of it -- `hp.held[env * A + agent]`
+//                 is the flat window index of the 1.0 that write left in the agent's target plane (255: unknown).  All of
+//                 it sits under `if constexpr (HELD)`: the other instances do not see it.
+template <int G, bool MW, bool P16, bool ROLL, bool BIG, bool PC, bool HELD, typename P, typename R, typename H = int>
+__device__ __forceinline__ void step_body(P& p, R& rp, const int t, const int slot, Carry& c, [[maybe_unused]] const H& hp = H{}) {
     static_assert(!MW || G == 64, "multi-wave environments use full waves");
+    static_assert(!HELD || (P16 && !ROLL && !BIG && !PC), "the held stream exists for the packed-row single-step kernels");
     static_assert(!BIG || MW, "the large-map layout runs one environment per workgroup");
     static_assert(!PC || (ROLL && !MW && P16), "the resolver / streamer pair exists for single-wave rollouts with packed rows");
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -951,6 +982,9 @@ __device__ __forceinline__ void step_body(P& p, R& rp, const int t, const int sl
     if constexpr (PC) {
         if (!do_stream) return;  // the resolver's iteration ends here; the pair meets at the barrier in rollout_kernel
     }
+    if constexpr (HELD) {  // the skip bitmap has an LDS region of its own behind everything else: cleared in front of this
+        for (int i = tid; i < hp.words; i += NT) smem[hp.lds_word + i] = 0u;  // barrier, filled behind it, read in phase 4
+    }
     lds_sync<MW>();
     if (when_stores == 1) emit_state(pos, tgt, active, elapsed, macc, so);
     int out_slot = slot;
@@ -973,6 +1007,10 @@ __device__ __forceinline__ void step_body(P& p, R& rp, const int t, const int sl
         // ---- phase 3 (P16): row masks -> registers -> (sync) -> packed u16 rows over the dead state -------
         const uint32_t wmask = (1u << W) - 1u;
         constexpr int RW = WT ? (WT + 1) / 2 : 8;  // words per item: two 16-bit rows each
+        [[maybe_unused]] uint32_t held_was = 255u;  // HELD: where the buffer's target plane of agent `tid` has its 1.0
+        if constexpr (HELD) {                       // (issued in front of the row items, used behind them)
+            if (tid < nag && !hp.refresh) held_was = hp.held[(size_t)env0 * A + tid];
+        }
         uint32_t rp[3][RW];  // W rows x 16 bit per item, 3 items per lane (nag * 3 <= 3 * NT)
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
@@ -1039,6 +1077,28 @@ __device__ __forceinline__ void step_body(P& p, R& rp, const int t, const int sl
                     const uint32_t val = (1u << (r - dy)) << (16 * (hit & 1));
 #pragma unroll
                     for (int m = 0; m < RW; ++m) rp[t][m] = (m == (hit >> 1)) ? val : 0u;
+                }
+            }
+        }
+        if constexpr (HELD) {
+            // Thread la, agent la of the slice: the plane's 1.0 of this write is recorded; every aligned unit wholly inside
+            // the plane that holds neither the 1.0 the buffer has nor the new one keeps its zeros and is flagged.
+            if (tid < nag) {
+                const int la = tid;
+                const uint32_t cell = s_apos[la], tc = s_atgt[la];
+                const int dx = max(-r, min(r, (int)(cell >> 16) - (int)(tc >> 16)));
+                const int dy = max(-r, min(r, (int)(cell & 0xFFFFu) - (int)(tc & 0xFFFFu)));
+                const uint32_t now = (uint32_t)((r - dx) * W + (r - dy));
+                hp.held[(size_t)env0 * A + la] = (uint8_t)now;
+                if (held_was < (uint32_t)(W * W)) {
+                    constexpr int UL = PGX_HELD_UNIT_LOG2;
+                    const uintptr_t slice = reinterpret_cast<uintptr_t>(obs_out + (size_t)env0 * A * 3 * W * W);
+                    const uintptr_t plane = slice + (size_t)(la * 3 + 2) * (size_t)(W * W) * 4;
+                    const uintptr_t ub = slice >> UL;
+                    const int u1 = (int)(((plane + (size_t)(W * W) * 4) >> UL) - ub);
+                    const int uw = (int)(((plane + held_was * 4) >> UL) - ub), un = (int)(((plane + now * 4) >> UL) - ub);
+                    for (int u = (int)(((plane + ((1u << UL) - 1u)) >> UL) - ub); u < u1; ++u)
+                        if (u != uw && u != un) atomicOr(&smem[hp.lds_word + (u >> 5)], 1u << (u & 31));
                 }
             }
         }
@@ -1126,6 +1186,13 @@ __device__ __forceinline__ void step_body(P& p, R& rp, const int t, const int sl
         const bool span = MW && !(p.flags & 512u);
         const int part = (nvec + nw - 1) / nw;
         const int q0 = span ? wave * part + lane : tid, q1 = span ? min(nvec, (wave + 1) * part) : nvec;
+        if constexpr (HELD) {
+            const uintptr_t o4 = reinterpret_cast<uintptr_t>(out + head);
+            const int a0 = (int)((o4 >> 4) - ((reinterpret_cast<uintptr_t>(out) >> PGX_HELD_UNIT_LOG2) << (PGX_HELD_UNIT_LOG2 - 4)));
+            stream_rows16_span<true, true>(reinterpret_cast<f32x4_t*>(out + head), reinterpret_cast<const uint32_t*>(rows16), head, W,
+                                           magic, (uint32_t)p.store_policy, q0, q1, span ? 64 : NT, (nag * 3 * W) >> 1,
+                                           smem + hp.lds_word, a0, hp.words - 1);
+        } else
         stream_rows16_span<true>(reinterpret_cast<f32x4_t*>(out + head), reinterpret_cast<const uint32_t*>(rows16), head, W, magic,
                            (uint32_t)p.store_policy, q0, q1, span ? 64 : NT, (nag * 3 * W) >> 1);
         if (when_stores == 2) emit_state(pos, tgt, active, elapsed, macc, so);
@@ -1252,7 +1319,16 @@ template <int G, bool MW, bool P16, bool BIG = false>
 __global__ __launch_bounds__(MW ? 1024 : 64, MW ? 1 : 8) void step_kernel(const StepParams p) {
     const RolloutParams none{};
     Carry unused;
-    step_body<G, MW, P16, false, BIG, false>(p, none, 0, 0, unused);
+    step_body<G, MW, P16, false, BIG, false, false>(p, none, 0, 0, unused);
+}
+
+// pgx_step_held: step_kernel<G, MW, true> whose observation stream leaves out the target-plane zeros that the output set
+// still holds (step_body, HELD).  Same launch shape as step_kernel; the skip bitmap lies behind that kernel's LDS.
+template <int G, bool MW>
+__global__ __launch_bounds__(MW ? 1024 : 64, MW ? 1 : 8) void step_held(const StepParams p, const HeldParams hp) {
+    const RolloutParams none{};
+    Carry unused;
+    step_body<G, MW, true, false, false, false, true>(p, none, 0, 0, unused, hp);
 }
 
 // K steps in ONE launch (pgx_rollout).  Environments never interact, so a workgroup can run its own environments
@@ -1297,7 +1373,7 @@ __global__ __launch_bounds__(MW ? 1024 : (PC ? 128 : 64), MW ? 1 : PGX_ROLL_OCC)
         asm volatile("" : "+s"(ka));
         KP& p = *reinterpret_cast<KP*>(ka);
         KR& rp = *reinterpret_cast<KR*>(ka + rp_offset);
-        step_body<G, MW, P16, true, BIG, PC>(p, rp, t, slot, c);
+        step_body<G, MW, P16, true, BIG, PC, false>(p, rp, t, slot, c);
         slot = slot + 1 == slots ? 0 : slot + 1;
         if ((t & 7) == 7) c.ablk = c.anext;
         if constexpr (MW || PC) lds_sync<true>();
@@ -1669,6 +1745,49 @@ int xcd_partition(int blocks, const float w[8], int32_t n[8], int32_t base[8]) {
         if (n[x] > grid) grid = n[x];
     }
     return grid * 8;
+}
+
+// The held form of the launch (pgx_step_held): float32 observations, packed rows, not the large-map layout.
+static const void* held_fn_for(const StepGeometry& g) {
+    if (g.big || !g.p16) return nullptr;
+    if (g.multi_wave) return reinterpret_cast<const void*>(&step_held<64, true>);
+#define PGX_CASE(gg) case gg: return reinterpret_cast<const void*>(&step_held<gg, false>);
+    switch (g.G) {
+        PGX_CASE(1) PGX_CASE(2) PGX_CASE(4) PGX_CASE(8) PGX_CASE(16) PGX_CASE(32) PGX_CASE(64)
+        default: return nullptr;
+    }
+#undef PGX_CASE
+}
+
+// words of the skip bitmap of one workgroup's slice (`slice_bytes` of observations at any alignment)
+static int held_words(size_t slice_bytes) {
+    const size_t units = (slice_bytes >> PGX_HELD_UNIT_LOG2) + 2;
+    return (int)(units / 32 + 1);
+}
+
+bool held_available(const StepGeometry& g, int A, int W, int obs_elem_bytes) {
+    if (!held_fn_for(g) || obs_elem_bytes != 4 || W > 15) return false;
+    const size_t slice = (size_t)g.epw * A * 3 * W * W * 4;
+    return g.lds_bytes + (size_t)held_words(slice) * 4 <= 160 * 1024;
+}
+
+hipError_t prepare_step_held(const StepGeometry& g, int A, int W) {
+    const size_t slice = (size_t)g.epw * A * 3 * W * W * 4;
+    return raise_lds_limit(held_fn_for(g), g.lds_bytes + (size_t)held_words(slice) * 4);
+}
+
+hipError_t launch_step_held(const StepParams& p, const StepGeometry& g, uint8_t* held, bool refresh, hipStream_t stream) {
+    const void* fn = held_fn_for(g);
+    if (!fn) return hipErrorInvalidValue;
+    StepParams args = p;
+    HeldParams h;
+    const int W = 2 * p.r + 1;
+    h.held = held;
+    h.refresh = refresh ? 1 : 0;
+    h.lds_word = (int32_t)(g.lds_bytes / 4);
+    h.words = held_words((size_t)g.epw * p.num_agents * 3 * W * W * 4);
+    void* kargs[] = {&args, &h};
+    return hipLaunchKernel(fn, dim3(g.grid), dim3(64 * g.waves), kargs, g.lds_bytes + (size_t)h.words * 4, stream);
 }
 
 hipError_t launch_step(const StepParams& p, const StepGeometry& g, hipStream_t stream) {

@@ -110,6 +110,15 @@ class VecPogema(PlacementMixin, QueryMixin):
     allocator and `placement["fallback"]` says why.  `close()` keeps one set of zone buffers mapped for the next
     environment of the same shape (buffers.ParkedBuffers, PGX_POOL_CACHE_MB); `close(release=True)` does not.
 
+    `held_zeros` (reuse_buffers="recycle", float32 observations): when step() writes a recycled output set again it does not
+    send the target-plane zeros the set already holds (pgx_step_held; DESIGN.md sections 5 and 6) -- same outputs, ~20 % fewer
+    bytes.  The engine trusts a set only while the version counter torch keeps for its observation tensor stands where the
+    engine left it: a torch in-place operation on a returned `obs` or any view of it is fine (that set's next write rewrites
+    everything); a write torch does NOT see -- through `.data`, a DLPack / __cuda_array_interface__ consumer, a kernel given
+    `data_ptr()` -- is not allowed on a returned observation tensor while this is on.  None (default): on for observation
+    tensors of at least 128 MiB, where it was measured to pay; True / PGX_HELD_ZEROS=1: wherever the kernel exists; False /
+    PGX_HELD_ZEROS=0: never.  `held_zeros` (property) reports whether it is on, steps taken and full rewrites.
+
     `map_pool`: maps of one shape H x W (a uint8 / bool tensor or array [M, H, W], or a list of GridConfig-style maps:
     rows or text of '.' and '#') that reset(seed), reset_where() and auto_reset="regenerate" draw from ON THE DEVICE --
     env i runs pool map `map_index[i]`, picked from (seed, global env index, generation), with its agents placed as on
@@ -127,7 +136,8 @@ class VecPogema(PlacementMixin, QueryMixin):
     def __init__(self, grid_config: Optional[GridConfig] = None, batch: int = 1, device="cuda:0",
                  env_index_base: int = 0, auto_reset: Optional[bool] = None, reuse_buffers="recycle",
                  obs_dtype=torch.float32, semantics: Optional[Semantics] = None,
-                 placement_probe: Optional[bool] = None, placement_budget_gib=None, map_pool=None):
+                 placement_probe: Optional[bool] = None, placement_budget_gib=None, map_pool=None,
+                 held_zeros: Optional[bool] = None):
         self.grid_config = grid_config if grid_config is not None else GridConfig(num_agents=2)
         gc = self.grid_config
         pool = None
@@ -229,6 +239,16 @@ class VecPogema(PlacementMixin, QueryMixin):
         if rc != 0:
             raise ValueError(f"this GridConfig does not fit the engine: {self._lib.pgx_last_error().decode()} (README.md, Limits)")
         _lib.check(self._lib.pgx_create(C.byref(cfg), self.device_index, C.byref(self._handle)))
+        # Held zeros (pgx_step_held): a recycled output set that still holds the engine's previous write is not sent the
+        # target-plane zeros again (class docstring).  PGX_HELD_ZEROS=0 / held_zeros=False: every step is pgx_step.
+        # held_zeros / PGX_HELD_ZEROS: None / unset = on where it pays (_held_pays), True / "1" = wherever the kernel exists.
+        if held_zeros is None and os.environ.get("PGX_HELD_ZEROS") in ("0", "1"):
+            held_zeros = os.environ["PGX_HELD_ZEROS"] == "1"
+        self._held_on = ((self._held_pays() if held_zeros is None else bool(held_zeros)) and self.recycle
+                         and self.obs_dtype == torch.float32 and not self.regenerate
+                         and bool(self._lib.pgx_held_available(self._handle)))
+        self._held_steps = 0      # steps that took pgx_step_held / of those, the ones that had to rewrite everything
+        self._held_refreshes = 0
         self._bufs = None
         self._buf_i = 0
         self._shared = None
@@ -618,6 +638,20 @@ class VecPogema(PlacementMixin, QueryMixin):
     def _has_state(self):
         return self._initial is not None
 
+    # held_zeros=None: the smallest observation tensor for which step() takes the held kernel by itself.  Empirical
+    # (docs/EXPERIMENTS.md, "Held zeros"): 190 MB and more gain 17-28 %, 95 MB is neutral, launches of 18 MB and less are
+    # slower -- they are bound by latency, and the held kernel adds a dependent load and a few LDS atomics per workgroup.
+    HELD_MIN_BYTES = 128 << 20
+
+    def _held_pays(self) -> bool:
+        return int(np.prod(self.obs_shape)) * 4 >= self.HELD_MIN_BYTES
+
+    @property
+    def held_zeros(self) -> dict:
+        """Whether step() uses pgx_step_held on recycled output sets, how many steps took it and how many of those had to
+        rewrite the whole observation (first use of a set, a set written through by the caller or lent to somebody else)."""
+        return {"enabled": bool(self._held_on), "steps": self._held_steps, "refreshes": self._held_refreshes}
+
     def _outputs(self, with_obs: bool = True):
         if self.recycle:
             return self._recycled(with_obs)
@@ -692,7 +726,25 @@ class VecPogema(PlacementMixin, QueryMixin):
             if compute_obs and obs is None:
                 raise ValueError("out[obs] is None but compute_obs=True")
         else:
-            obs, rewards, terminated, truncated, is_active = self._outputs(compute_obs)
+            held = self._held_outputs(compute_obs) if self._held_on else None
+            if held is not None:
+                (obs, rewards, terminated, truncated, is_active), record, trusted, index = held
+                if compute_obs:
+                    _lib.check(self._lib.pgx_step_held(
+                        self._handle, actions.data_ptr(), self._ACTION_CODE[actions.dtype], obs.data_ptr(), record.data_ptr(),
+                        0 if trusted else 1, rewards.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
+                        is_active.data_ptr(), self._stream()))
+                    self._recycler.vouch(index)
+                    self._held_steps += 1
+                    self._held_refreshes += 0 if trusted else 1
+                    infos = {"is_active": is_active, "episode_done": self.episode_done, "metrics": self.metrics}
+                    if self.semantics.bad_action == "flag":
+                        self._raise_on_bad_actions()
+                    return self._wrap_obs(obs), rewards, terminated, truncated, infos
+            elif self._held_on and self._recycler and not torch.cuda.is_current_stream_capturing():
+                obs, rewards, terminated, truncated, is_active = self._alloc_outputs(compute_obs)  # every set is referenced
+            else:
+                obs, rewards, terminated, truncated, is_active = self._outputs(compute_obs)
         _lib.check(self._lib.pgx_step(
             self._handle, actions.data_ptr(), self._ACTION_CODE[actions.dtype],
             obs.data_ptr() if compute_obs else None, rewards.data_ptr(), terminated.data_ptr(),
@@ -712,13 +764,26 @@ class VecPogema(PlacementMixin, QueryMixin):
                     self._shared.data_ptr() if self._shared is not None else None, 3,
                     obs.data_ptr() if compute_obs else None, self._stream()))
         if self.semantics.bad_action == "flag":  # the reference's IndexError on MOVES[action]; one host sync per step
-            bad = int(self._lib.pgx_bad_action_count(self._handle, self._stream()))
-            if bad < 0:
-                _lib.check(bad)
-            if bad:
-                raise IndexError(f"{bad} action(s) of active agents were outside 0..{len(self.grid_config.MOVES) - 1}")
+            self._raise_on_bad_actions()
         infos = {"is_active": is_active, "episode_done": self.episode_done, "metrics": self.metrics}
         return (self._wrap_obs(obs) if compute_obs else None), rewards, terminated, truncated, infos
+
+    def _raise_on_bad_actions(self):
+        bad = int(self._lib.pgx_bad_action_count(self._handle, self._stream()))
+        if bad < 0:
+            _lib.check(bad)
+        if bad:
+            raise IndexError(f"{bad} action(s) of active agents were outside 0..{len(self.grid_config.MOVES) - 1}")
+
+    def _held_outputs(self, with_obs: bool):
+        """A recycled output set for a held step -- (outputs, held record, trusted, set index) -- or None: no recycler (graph
+        capture, no state yet, hook missing) or every set still referenced; the step then runs as ever."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._recycler is None and self._has_state() and not capturing:
+            self._recycler = self._build_recycler()
+        if not self._recycler or capturing:
+            return None
+        return self._recycler.take_for_step(with_obs)
 
     def rollout(self, actions=None, obs_slots: Optional[int] = None, steps: Optional[int] = None, policy_seed: int = 0,
                 policy_step0: int = 0, record_actions: bool = True):
