@@ -754,6 +754,31 @@ int64_t pgx_snapshot_bytes(pgx_env* env);
 int pgx_save_snapshot(pgx_env* env, void* blob, void* stream);
 int pgx_load_snapshot(pgx_env* env, const void* blob, void* stream);
 
+/* ---- environment copies (docs/SPEC.md S19) -------------------------------------------------------- */
+/* Branching on the device: for every pair k < count, environment dst[k] becomes a copy of environment src[k] as it
+ * stood before the call -- agent and target cells, the auto-reset state, the active and ghost bits, the step counter,
+ * the metric accumulators, the map (u8 and padded bitmap, the `empty_outside=False` bits included), under
+ * on_target = restart the draw counters, the numpy generators and the component tables, and with a map pool the pool
+ * index.  What belongs to the SLOT stays: the generation counter (a later regenerate / masked reset of dst[k] draws
+ * what that slot would have drawn next) and the global env index every counter-based stream is keyed on (the default
+ * lifelong stream, the random policy of pgx_rollout): the copy draws what env dst[k] draws at the copied counters.
+ *   src, dst  device i32 [count].  One source may feed many destinations; src[k] == dst[k] is a no-op.  A pair with an
+ *             index outside 0..batch-1 is skipped: nothing is read or written out of range.  Not supported (the result
+ *             is unspecified for the envs involved, every other env is untouched): a destination given twice, and an
+ *             env that is the destination of one pair and the source of another (no permutations, no swaps).
+ *   flags     0, or PGX_COPY_NO_CACHE: leave the distance-field cache alone.  By default, when the cache is allocated,
+ *             the pairs' rows of it (tags, map bits, fields) are copied too, so that queries after a branch build
+ *             nothing; without them the next refresh rebuilds what no longer matches.  Results are the same either
+ *             way, only pgx_cost_to_go_builds differs.  The call never allocates the cache.
+ * Rows of map-sized arrays are skipped for a pair whose two envs already hold equal maps (a compare pass decides per
+ * pair), so a branch inside one map moves ~17 bytes per agent.  Two kernel launches, three with the cache; allocates
+ * nothing, asynchronous on `stream`, no host sync, capturable in a HIP graph.  Caller-owned outputs (observations,
+ * metrics, episode_done) are not touched: the next pgx_step / pgx_observe shows the copied state.
+ * PGX_E_INVALID, checked before the handle (no device needed), for a negative count, a NULL src or dst with count > 0,
+ * unknown flag bits and a NULL env; PGX_E_STATE before the first reset.  count == 0: PGX_OK, nothing is launched. */
+#define PGX_COPY_NO_CACHE 1
+int pgx_copy_envs(pgx_env* env, const int32_t* src, const int32_t* dst, int32_t count, int32_t flags, void* stream);
+
 /* ---- host-side synthetic map generator ------------------------------------------------------------ */
 /* Fills host buffers with `batch` random solvable instances: Bernoulli(density) obstacles, starts and
  * targets on distinct free cells with each start/target pair in one 4-connected component.

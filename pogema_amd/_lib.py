@@ -65,6 +65,7 @@ NUM_OUTCOMES = len(OUTCOMES)  # PGX_NUM_OUTCOMES
 # PGX_CHANNEL_*: the planes of pgx_policy_input, name -> code (docs/SPEC.md S18); its dtype table is OBS_DTYPES (PGX_OBS_*)
 POLICY_CHANNELS = {"obstacles": 0, "agents": 1, "target": 2, "other_goals": 3, "up": 4, "down": 5, "left": 6, "right": 7}
 NUM_CHANNELS = len(POLICY_CHANNELS)  # PGX_NUM_CHANNELS
+COPY_NO_CACHE = 1  # PGX_COPY_NO_CACHE: flag of pgx_copy_envs (docs/SPEC.md S19)
 DEFAULT_POLICY_CHANNELS = ("obstacles", "agents", "target", "up", "down", "left", "right")
 
 
@@ -78,7 +79,7 @@ EXPORTED_SYMBOLS = (
     "pgx_expert_actions", "pgx_set_map_pool", "pgx_reset_pool", "pgx_regenerate_pool", "pgx_get_map_index",
     "pgx_cost_to_go", "pgx_cost_to_go_bytes", "pgx_cost_to_go_builds", "pgx_visible_agents", "pgx_pibt_actions",
     "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan", "pgx_move_outcomes",
-    "pgx_policy_input",
+    "pgx_policy_input", "pgx_copy_envs",
 )
 
 
@@ -208,6 +209,8 @@ def load() -> C.CDLL:
     lib.pgx_move_outcomes.restype = C.c_int
     lib.pgx_policy_input.argtypes = [vp, C.POINTER(i32), i32, i32, vp, vp]
     lib.pgx_policy_input.restype = C.c_int
+    lib.pgx_copy_envs.argtypes = [vp, vp, vp, i32, i32, vp]
+    lib.pgx_copy_envs.restype = C.c_int
     lib.pgx_set_map_pool.argtypes = [vp, vp, i32, vp, vp]
     lib.pgx_set_map_pool.restype = C.c_int
     lib.pgx_reset_pool.argtypes = [vp, u64, vp, i32, vp]

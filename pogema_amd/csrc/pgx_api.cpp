@@ -136,6 +136,7 @@ struct pgx_env {
     // cost-to-go cache (docs/SPEC.md S11, pgx::cost_to_go_layout), allocated by the first pgx_cost_to_go,
     // pgx_pibt_actions, pgx_pibt_plan, pgx_goal_directions or pgx_policy_input with a direction channel
     DevBuf<uint8_t> c2g;
+    DevBuf<uint8_t> copy_same;            // [B] pgx_copy_envs: 1 where the destination env already holds its source's map
 };
 
 namespace {
@@ -402,6 +403,7 @@ static int create_device_side(pgx_env* e) {
     alloc(e->fail_count, sizeof(uint32_t));
     alloc(e->regen_fail, sizeof(uint32_t));
     alloc(e->bad_count, sizeof(uint32_t));
+    alloc(e->copy_same, B);
     if (cfg->on_target == PGX_ON_TARGET_RESTART) {
         const size_t cells = B * (size_t)cfg->height * cfg->width;
         alloc(e->comp_begin, cells * sizeof(uint32_t));
@@ -790,27 +792,40 @@ int pgx_get_map_index(pgx_env* e, int32_t* out, void* stream) {
 // ---- snapshot / restore of the complete engine state (checkpoint-resume, `step_back`) ---------------------
 extern "C++" {
 namespace {
+// One array of the per-environment state: `bytes` in all, `row` bytes per env.  What the array is to a copy of one env
+// onto another slot (pgx_copy_envs; save / load take every segment whole): SEG_STATE is copied, SEG_MAP is copied unless
+// both envs hold the same map (it is a function of the map), SEG_SLOT belongs to the slot and stays.
+enum SegKind { SEG_STATE = 0, SEG_MAP = 1, SEG_SLOT = 2 };
 struct Segment {
     void* ptr;
     size_t bytes;
+    size_t row;
+    SegKind kind;
 };
 // with_pool: the layout of a handle with a map pool installed (map_index appended as the last segment)
 std::vector<Segment> snapshot_segments(pgx_env* e, bool with_pool) {
     const pgx_config& c = e->cfg;
-    const size_t B = (size_t)c.batch, BA = B * c.num_agents, cells = (size_t)c.height * c.width;
-    std::vector<Segment> seg = {
-        {e->pos, BA * 4}, {e->tgt, BA * 4}, {e->pos0, BA * 4}, {e->tgt0, BA * 4}, {e->active, BA},
-        {e->elapsed, B * 4}, {e->macc, B * sizeof(int4)}, {e->epoch, B * 4}, {e->map_u8, B * cells},
-        {e->obst, B * e->bmw * 4},
-    };
+    const size_t B = (size_t)c.batch, A = (size_t)c.num_agents, cells = (size_t)c.height * c.width;
+    std::vector<Segment> seg;
+    auto add = [&](void* ptr, size_t row, SegKind kind) { seg.push_back({ptr, B * row, row, kind}); };
+    add(e->pos, A * 4, SEG_STATE);
+    add(e->tgt, A * 4, SEG_STATE);
+    add(e->pos0, A * 4, SEG_STATE);
+    add(e->tgt0, A * 4, SEG_STATE);
+    add(e->active, A, SEG_STATE);
+    add(e->elapsed, 4, SEG_STATE);
+    add(e->macc, sizeof(int4), SEG_STATE);
+    add(e->epoch, 4, SEG_SLOT);  // the generation counter: the slot's next instance stays the slot's
+    add(e->map_u8, cells, SEG_MAP);
+    add(e->obst, (size_t)e->bmw * 4, SEG_MAP);
     if (c.on_target == PGX_ON_TARGET_RESTART) {
-        seg.push_back({e->tcount, BA * 4});
-        if (e->np_state) seg.push_back({e->np_state, BA * sizeof(pgx::NpGen)});
-        seg.push_back({e->comp_begin, B * cells * 4});
-        seg.push_back({e->comp_len, B * cells * 4});
-        seg.push_back({e->comp_cells, B * cells * 4});
+        add(e->tcount, A * 4, SEG_STATE);
+        if (e->np_state) add(e->np_state, A * sizeof(pgx::NpGen), SEG_STATE);
+        add(e->comp_begin, cells * 4, SEG_MAP);
+        add(e->comp_len, cells * 4, SEG_MAP);
+        add(e->comp_cells, cells * 4, SEG_MAP);
     }
-    if (with_pool) seg.push_back({e->map_index, B * 4});
+    if (with_pool) add(e->map_index, 4, SEG_STATE);
     return seg;
 }
 size_t aligned16(size_t n) { return (n + 15) & ~(size_t)15; }
@@ -894,6 +909,50 @@ int pgx_load_snapshot(pgx_env* e, const void* blob, void* stream) {
     }
     if (e->map_index && !with_pool) PGX_HIP(hipMemsetAsync(e->map_index, 0xFF, (size_t)e->cfg.batch * sizeof(int32_t), s));
     e->has_state = true;
+    return PGX_OK;
+}
+
+// ---- environment copies (docs/SPEC.md S19) ---------------------------------------------------------------
+int pgx_copy_envs(pgx_env* e, const int32_t* src, const int32_t* dst, int32_t count, int32_t flags, void* stream) {
+    static const char who[] = "pgx_copy_envs";
+    if (count < 0) return fail_msg(PGX_E_INVALID, "%s: count must be >= 0, got %d", who, count);
+    if (count > 0 && !src) return fail_msg(PGX_E_INVALID, "%s: src is null", who);
+    if (count > 0 && !dst) return fail_msg(PGX_E_INVALID, "%s: dst is null", who);
+    if (const int rc = check_flags(who, flags, PGX_COPY_NO_CACHE)) return rc;
+    if (!e) return fail_msg(PGX_E_INVALID, "%s: env is null", who);
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    if (count == 0) return PGX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const pgx_config& c = e->cfg;
+    pgx::CopyParams p;
+    memset(&p, 0, sizeof p);
+    p.src = src;
+    p.dst = dst;
+    p.count = count;
+    p.batch = c.batch;
+    for (const Segment& g : snapshot_segments(e, e->map_index != nullptr)) {
+        if (g.kind == SEG_SLOT) continue;
+        if (p.nseg == pgx::COPY_MAX_SEGS) return fail_msg(PGX_E_STATE, "%s: more than %d state segments", who, pgx::COPY_MAX_SEGS);
+        pgx::CopySeg& q = p.seg[p.nseg++];
+        q.base = static_cast<char*>(g.ptr);
+        q.row = g.row;
+        q.of_map = g.kind == SEG_MAP ? 1 : 0;
+    }
+    p.chunks = pgx::copy_plan_chunks(p.seg, p.nseg, count);
+    PGX_HIP(pgx::launch_copy_compare(p, e->obst, e->bmw, e->map_index, e->copy_same, s));
+    PGX_HIP(pgx::launch_copy_rows(p, e->copy_same, s));
+    if (e->c2g && !(flags & PGX_COPY_NO_CACHE)) {  // the pairs' rows of the distance-field cache: nothing to rebuild after a branch
+        const pgx::CostToGoLayout l = pgx::cost_to_go_layout(c.batch, c.num_agents, c.height, c.width);
+        const size_t cells = (size_t)c.height * c.width, A = (size_t)c.num_agents;
+        pgx::CopyParams q = p;
+        q.nseg = 3;
+        q.seg[0] = {reinterpret_cast<char*>(e->c2g.p) + l.tag_off, A * sizeof(uint32_t), 0, 0, 0, 0};
+        q.seg[1] = {reinterpret_cast<char*>(e->c2g.p) + l.map_off, (size_t)c.height * ((c.width + 31) / 32) * sizeof(uint32_t), 0, 0, 0, 0};
+        q.seg[2] = {reinterpret_cast<char*>(e->c2g.p) + l.field_off, A * cells * l.cell_bytes, 0, 0, 0, 0};
+        q.chunks = pgx::copy_plan_chunks(q.seg, q.nseg, count);
+        PGX_HIP(pgx::launch_copy_rows(q, nullptr, s));
+    }
     return PGX_OK;
 }
 

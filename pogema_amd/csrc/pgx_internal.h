@@ -408,4 +408,34 @@ struct OutcomeParams : StateView {
 };
 hipError_t launch_move_outcomes(const OutcomeParams& p, hipStream_t stream);
 
+// ---- environment copies (pgx_copy.hip): rows of the per-env state arrays, slot to slot -------------------------------
+constexpr size_t COPY_CHUNK_VECS = 1024;   // a slice of a large row is at least this many 16-byte pieces (16 KiB)
+constexpr size_t COPY_TARGET_GROUPS = 8192;  // workgroups a call spreads one array's large rows over, all pairs together
+constexpr size_t COPY_SMALL_ROW = 2048;    // rows up to this many bytes share the pair's first workgroup
+enum { COPY_MAX_SEGS = 16 };
+struct CopySeg {
+    char* base;              // [B][row] bytes
+    size_t row;
+    uint32_t chunk0, nchunks;  // the workgroups of a pair that copy this row (copy_plan_chunks)
+    int32_t of_map;          // a function of the env's map: left alone where source and destination hold equal maps
+    int32_t reserved0;
+};
+struct CopyParams {
+    const int32_t* src;      // [count] device
+    const int32_t* dst;      // [count] device
+    int32_t count, batch;
+    int32_t pair0;           // first pair of this launch
+    uint32_t chunks;         // workgroups per pair
+    int32_t nseg;
+    int32_t reserved0;
+    CopySeg seg[COPY_MAX_SEGS];
+};
+// fills chunk0 / nchunks of every segment from its row size and the number of pairs; returns the workgroups per pair
+uint32_t copy_plan_chunks(CopySeg* seg, int nseg, int count);
+// same_map[dst[k]] = 1 iff the padded bitmaps (and, with `map_index`, the pool indices) of src[k] and dst[k] are equal
+hipError_t launch_copy_compare(CopyParams p, const uint32_t* obst, int bmw, const int32_t* map_index, uint8_t* same_map,
+                               hipStream_t stream);
+// the rows of every pair; `same_map` (may be null) as launch_copy_compare left it
+hipError_t launch_copy_rows(CopyParams p, const uint8_t* same_map, hipStream_t stream);
+
 }  // namespace pgx

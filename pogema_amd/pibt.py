@@ -39,6 +39,21 @@ class PibtPolicy:
                                                                      out=out)
         return actions, path_xy, arrival
 
+    def copy_envs(self, src, dst, *, cache: bool = True, validate: bool = True) -> None:
+        """`env.copy_envs(src, dst)` (docs/SPEC.md S19) with the policy's priorities: row dst[k] of `self.priority`
+        becomes row src[k], so that act() on a copy equals act() on its source.  A pair the engine skips (an index
+        outside 0..batch-1 under `validate=False`) is skipped here too."""
+        from .vec_env import copy_pairs
+        B = self.env.batch
+        s, d = copy_pairs(src, dst, B, validate)
+        s, d = s.to(self.priority.device).long(), d.to(self.priority.device).long()
+        ok = (s >= 0) & (s < B) & (d >= 0) & (d < B)
+        spare = torch.full_like(d, B)  # a skipped pair moves the spare row B onto itself: no host sync, no clash
+        rows = torch.cat([self.priority, self.priority.new_zeros((1, self.priority.shape[1]))])
+        rows.index_copy_(0, torch.where(ok, d, spare), rows.index_select(0, torch.where(ok, s, spare)))
+        self.priority = rows[:B]
+        self.env.copy_envs(src, dst, cache=cache, validate=False)
+
     def update(self, rewards, episode_done=None) -> None:
         """Priority becomes 0 where the agent got a positive reward in this step, stands on its target, is inactive, or
         its env's episode finished (`episode_done`: bool / uint8 [batch], e.g. step()'s infos["episode_done"]);

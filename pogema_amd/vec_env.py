@@ -67,6 +67,65 @@ def parse_map_pool(maps) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(np.stack(out)))
 
 
+def copy_pairs(src, dst, batch: int, validate: bool = True):
+    """The (src, dst) of copy_envs() as two 1-D integer tensors of one length, on whatever device they came from (ints,
+    sequences and arrays: the host).  `src` may be one int, broadcast over `dst`.  Anything but int32 / int64 indices,
+    or lengths that differ, is a ValueError.  `validate`: every index lies in 0..batch-1, no destination is given twice
+    and no destination of a pair with src != dst is the source of another such pair -- a ValueError names the first
+    offending entry.  Host indices are checked on the host; device tensors with ONE synchronising read.  Needs no
+    engine and no GPU."""
+    def as_tensor(name, v):
+        if isinstance(v, torch.Tensor):
+            t = v.detach()
+        else:
+            a = np.asarray(v)
+            if a.size == 0:
+                a = a.astype(np.int64)
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"{name} must hold integer env indices, got {a.dtype}")
+            t = torch.from_numpy(a.astype(np.int64))  # (astype copies: contiguous, 0-d stays 0-d)
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{name} must be an int32 or int64 tensor, got {t.dtype}")
+        return t
+
+    d = as_tensor("dst", dst)
+    if d.dim() != 1:
+        raise ValueError(f"dst must be a sequence or a 1-D tensor of env indices, got shape {tuple(d.shape)}")
+    s = as_tensor("src", src)
+    if s.dim() == 0:
+        s = s.to(d.device).to(d.dtype).expand(d.numel()).contiguous()
+    if s.dim() != 1 or s.numel() != d.numel():
+        raise ValueError(f"src has {s.numel()} entries and dst has {d.numel()}: copy_envs() works on pairs (src[k], dst[k])")
+    if validate and d.numel():
+        if s.device != d.device:
+            s = s.to(d.device)
+        s64, d64, n = s.long(), d.long(), d.numel()
+
+        def first(mask):  # index of the first set entry, -1 when none
+            return torch.where(mask.any(), mask.to(torch.uint8).argmax(), torch.full((), -1, dtype=torch.int64, device=mask.device))
+
+        bad_s, bad_d = (s64 < 0) | (s64 >= batch), (d64 < 0) | (d64 >= batch)
+        sc, dc = s64.clamp(0, batch - 1), d64.clamp(0, batch - 1)
+        order = torch.argsort(dc, stable=True)
+        twice = torch.zeros(n, dtype=torch.bool, device=d.device)
+        twice[order[1:]] = dc[order[1:]] == dc[order[:-1]]
+        real = sc != dc  # (a pair with src == dst is a no-op: its env is neither read nor written)
+        is_src = torch.zeros(batch, dtype=torch.bool, device=d.device)
+        is_src[sc[real]] = True
+        also_src = real & is_src[dc]
+        k_s, k_d, k_t, k_a = torch.stack([first(bad_s), first(bad_d), first(twice), first(also_src)]).tolist()  # the one sync
+        if k_s >= 0:
+            raise ValueError(f"src[{k_s}] = {int(s64[k_s])} is outside 0..{batch - 1}")
+        if k_d >= 0:
+            raise ValueError(f"dst[{k_d}] = {int(d64[k_d])} is outside 0..{batch - 1}")
+        if k_t >= 0:
+            raise ValueError(f"dst[{k_t}] = {int(d64[k_t])} is given twice: every destination takes one copy")
+        if k_a >= 0:
+            raise ValueError(f"dst[{k_a}] = {int(d64[k_a])} is also a source: copy_envs() does no permutations or swaps "
+                             f"(copy through a free slot, or in two calls)")
+    return s, d
+
+
 class VecPogema(PlacementMixin, QueryMixin):
     """`batch` independent POGEMA environments on one MI355X.
 
@@ -909,6 +968,38 @@ class VecPogema(PlacementMixin, QueryMixin):
             out["global_xy"] = st["agents_xy"]
             out["global_target_xy"] = st["targets_xy"]
         return out
+
+    def copy_envs(self, src, dst, *, cache: bool = True, validate: bool = True) -> None:
+        """Branching on the device (docs/SPEC.md S19): for every pair, environment dst[k] becomes a copy of environment
+        src[k] as it stood before the call -- cells, targets, auto-reset state, active and ghost bits, `elapsed`, the
+        metric accumulators, the map, and under on_target="restart" the draw counters, generators and component tables;
+        with a map pool also `map_index`.  The slot keeps its generation counter and its global env index: a later
+        reset_where() / auto_reset="regenerate" of dst[k] draws what that slot would have drawn, and the default
+        lifelong stream and rollout(None)'s policy stay keyed on dst[k]'s index (with lifelong_rng="numpy" the copy
+        draws its source's targets: the generators are copied).
+        `src`: an int (broadcast), a sequence or an int32 / int64 tensor on any device; `dst`: a sequence or a tensor.
+        One source may feed many destinations; src[k] == dst[k] is a no-op.  Not supported: a destination given twice,
+        an env that is the destination of one pair and the source of another.
+        `validate` (default on): range, equal lengths, distinct destinations, no destination that is also a source --
+        on the host for sequences and CPU tensors, with one synchronising read for device tensors; a ValueError names
+        the offending entry.  `validate=False` skips it: the engine still skips a pair with an index outside
+        0..batch-1 (nothing is accessed out of range), and with int32 tensors on this device the call allocates
+        nothing, never syncs and can be captured in a HIP graph.
+        `cache` (default on): the pairs' rows of the distance-field cache of cost_to_go() / pibt_actions() /
+        goal_directions() are copied too when that cache exists, so that queries after a branch build nothing; False
+        leaves it to the next query's refresh.  Same results either way; only `cost_to_go_builds` differs.
+        Outputs of earlier calls (observations, infos, metrics) are not touched: the next step() / observe() shows the
+        copied state.  Copies between two engines are not supported."""
+        s, d = copy_pairs(src, dst, self.batch, validate)
+        s = s.to(self.device).to(torch.int32).contiguous()
+        d = d.to(self.device).to(torch.int32).contiguous()
+        _lib.check(self._lib.pgx_copy_envs(self._handle, s.data_ptr(), d.data_ptr(), d.numel(),
+                                           0 if cache else _lib.COPY_NO_CACHE, self._stream()))
+        if self._initial is not None and self.observation_type != "default":
+            # the dict views report cells relative to the initial state: the copy's is its source's (one host sync)
+            ok = ((s >= 0) & (s < self.batch) & (d >= 0) & (d < self.batch))
+            s64, d64 = s[ok].long(), d[ok].long()
+            self._initial = tuple(t.clone().index_copy_(0, d64, t.index_select(0, s64)) for t in self._initial)
 
     # ------------------------------------------------------------------------------------------
     def save_state(self) -> torch.Tensor:
