@@ -611,6 +611,51 @@ int pgx_goal_directions(pgx_env* env, int32_t flags, void* out, int32_t format, 
 #define PGX_NUM_CHANNELS 8
 int pgx_policy_input(pgx_env* env, const int32_t* channels, int32_t num_channels, int32_t dtype, void* out, void* stream);
 
+/* Global state (docs/SPEC.md S20): the picture of the whole map a centralised critic, a value mixer or a central planner
+ * reads, [batch, num_channels, H, W] with H, W the unpadded map size, row x, column y (pgx_get_map's orientation,
+ * pgx_get_state's coordinates), written once, in the order and the number format the caller takes -- read from the
+ * current device state, the state the next pgx_step reads, which this call does not change.  Plane c is the channel
+ * channels[c]; its value at cell (x, y):
+ *   PGX_GLOBAL_OBSTACLES   pgx_get_map's byte of the env as it is now (after regeneration, pool draws and pgx_copy_envs),
+ *                          bit for bit for the 0 / 1 maps the engine installs
+ *   PGX_GLOBAL_AGENTS      the interior of pgx_get_state's occupancy array, bit for bit: 1 iff an agent whose is_active
+ *                          byte is exactly 1 stands there (hidden agents and soft_occupancy ghosts are absent, as in
+ *                          observation plane 1)
+ *   PGX_GLOBAL_TARGETS     1 iff it is the target of at least one agent with bit 0 of is_active set (a ghost's target
+ *                          counts, a finished, hidden agent's does not)
+ *   PGX_GLOBAL_AGENT_IDS   i + 1 for the lowest index i among the agents PGX_GLOBAL_AGENTS counts on the cell, else 0
+ *   PGX_GLOBAL_TARGET_IDS  j + 1 for the lowest index j among the agents PGX_GLOBAL_TARGETS counts whose target is the
+ *                          cell, else 0 (lifelong targets may coincide)
+ *   channels      host array of num_channels distinct PGX_GLOBAL_* codes, read before the call returns
+ *   num_channels  1..PGX_NUM_GLOBAL_CHANNELS
+ *   dtype         PGX_OBS_F32, PGX_OBS_U8, PGX_OBS_BF16 or PGX_OBS_F16: the elements of `out`; chosen per call, whatever
+ *                 obs_dtype the handle was created with.  With an id channel the format must hold num_agents exactly:
+ *                 PGX_OBS_U8 up to PGX_GLOBAL_ID_MAX_U8 agents, PGX_OBS_BF16 up to PGX_GLOBAL_ID_MAX_BF16, the other two
+ *                 every count the engine accepts
+ *   out           device buffer [batch, num_channels, H, W] of dtype, must not be NULL, aligned to its element size.  A
+ *                 16-byte aligned `out` is written with 16-byte stores but for the few elements around a plane whose
+ *                 start is not 16-byte aligned (odd H * W in a narrow format); any other `out` works the same way,
+ *                 with those few elements at every plane.
+ * One launch that allocates nothing: asynchronous on `stream`, no host sync, capturable in a HIP graph from the first
+ * call after a reset; pgx_cost_to_go_builds does not move.  A workgroup holds a band of whole rows of at most
+ * PGX_GLOBAL_BAND_CELLS cells at a time (PGX_GLOBAL_BAND_CELLS / W rows).  PGX_E_INVALID for a NULL `channels` or `out`,
+ * a count outside 1..PGX_NUM_GLOBAL_CHANNELS, a code outside 0..4 or given twice, an unknown dtype, a misaligned `out` or
+ * an id channel in a format too narrow for the handle's num_agents (all checked before the device is touched);
+ * PGX_E_STATE before the first reset, like pgx_step.
+ * pgx_global_state_check makes the same argument checks, in the same order and with the same messages, for an engine of
+ * `num_agents` agents without a handle: PGX_OK where pgx_global_state would go on to the handle. */
+#define PGX_GLOBAL_OBSTACLES 0
+#define PGX_GLOBAL_AGENTS 1
+#define PGX_GLOBAL_TARGETS 2
+#define PGX_GLOBAL_AGENT_IDS 3
+#define PGX_GLOBAL_TARGET_IDS 4
+#define PGX_NUM_GLOBAL_CHANNELS 5
+#define PGX_GLOBAL_ID_MAX_U8 255
+#define PGX_GLOBAL_ID_MAX_BF16 256
+#define PGX_GLOBAL_BAND_CELLS 8192
+int pgx_global_state(pgx_env* env, const int32_t* channels, int32_t num_channels, int32_t dtype, void* out, void* stream);
+int pgx_global_state_check(int32_t num_agents, const int32_t* channels, int32_t num_channels, int32_t dtype, const void* out);
+
 /* Number of out-of-range actions (outside 0..4) that ACTIVE agents submitted since the last call (bad_action =
  * PGX_BAD_ACTION_FLAG only; otherwise always 0).  Inactive agents' actions are never looked at, as in the reference's
  * `if self.grid.is_active[agent_idx]` guards.  Synchronises `stream`, then clears the counter.  The host side turns a

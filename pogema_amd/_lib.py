@@ -67,6 +67,16 @@ POLICY_CHANNELS = {"obstacles": 0, "agents": 1, "target": 2, "other_goals": 3, "
 NUM_CHANNELS = len(POLICY_CHANNELS)  # PGX_NUM_CHANNELS
 COPY_NO_CACHE = 1  # PGX_COPY_NO_CACHE: flag of pgx_copy_envs (docs/SPEC.md S19)
 DEFAULT_POLICY_CHANNELS = ("obstacles", "agents", "target", "up", "down", "left", "right")
+# PGX_GLOBAL_*: the planes of pgx_global_state, name -> code (docs/SPEC.md S20); its dtype table is OBS_DTYPES too
+GLOBAL_CHANNELS = {"obstacles": 0, "agents": 1, "targets": 2, "agent_ids": 3, "target_ids": 4}
+NUM_GLOBAL_CHANNELS = len(GLOBAL_CHANNELS)  # PGX_NUM_GLOBAL_CHANNELS
+DEFAULT_GLOBAL_CHANNELS = ("obstacles", "agents", "targets")
+GLOBAL_ID_CHANNELS = ("agent_ids", "target_ids")
+# the most agents an id channel holds exactly, by PGX_OBS_* code (PGX_GLOBAL_ID_MAX_U8, PGX_GLOBAL_ID_MAX_BF16); the
+# other formats hold every count the engine accepts
+GLOBAL_ID_MAX = {1: 255, 2: 256}
+# PGX_GLOBAL_BAND_CELLS: a workgroup of pgx_global_state holds GLOBAL_BAND_CELLS // W whole rows of a map at a time
+GLOBAL_BAND_CELLS = 8192
 
 
 # every symbol include/pogema_amd.h declares; tests/test_abi.py checks the library exports them all
@@ -79,7 +89,7 @@ EXPORTED_SYMBOLS = (
     "pgx_expert_actions", "pgx_set_map_pool", "pgx_reset_pool", "pgx_regenerate_pool", "pgx_get_map_index",
     "pgx_cost_to_go", "pgx_cost_to_go_bytes", "pgx_cost_to_go_builds", "pgx_visible_agents", "pgx_pibt_actions",
     "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan", "pgx_move_outcomes",
-    "pgx_policy_input", "pgx_copy_envs",
+    "pgx_policy_input", "pgx_copy_envs", "pgx_global_state", "pgx_global_state_check",
 )
 
 
@@ -209,6 +219,10 @@ def load() -> C.CDLL:
     lib.pgx_move_outcomes.restype = C.c_int
     lib.pgx_policy_input.argtypes = [vp, C.POINTER(i32), i32, i32, vp, vp]
     lib.pgx_policy_input.restype = C.c_int
+    lib.pgx_global_state.argtypes = [vp, C.POINTER(i32), i32, i32, vp, vp]
+    lib.pgx_global_state.restype = C.c_int
+    lib.pgx_global_state_check.argtypes = [i32, C.POINTER(i32), i32, i32, vp]
+    lib.pgx_global_state_check.restype = C.c_int
     lib.pgx_copy_envs.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.pgx_copy_envs.restype = C.c_int
     lib.pgx_set_map_pool.argtypes = [vp, vp, i32, vp, vp]

@@ -1344,6 +1344,69 @@ int pgx_policy_input(pgx_env* e, const int32_t* channels, int32_t num_channels, 
     return PGX_OK;
 }
 
+// ---- global state (docs/SPEC.md S20) ------------------------------------------------------------------------
+namespace {
+// The argument checks of pgx_global_state, in pgx_policy_input's order, then the id-range rule for `num_agents` agents;
+// fills the kernel's picture of the channel list.
+int global_state_args(int32_t num_agents, const int32_t* channels, int32_t num_channels, int32_t dtype, const void* out,
+                      uint32_t* codes_out, uint32_t* need_out) {
+    static const char who[] = "pgx_global_state";
+    if (!out) return fail_msg(PGX_E_INVALID, "%s: out is null", who);
+    if (!channels) return fail_msg(PGX_E_INVALID, "%s: channels is null", who);
+    if (num_channels < 1 || num_channels > PGX_NUM_GLOBAL_CHANNELS)
+        return fail_msg(PGX_E_INVALID, "%s: num_channels %d is outside 1..%d", who, num_channels, PGX_NUM_GLOBAL_CHANNELS);
+    static_assert(PGX_NUM_GLOBAL_CHANNELS == pgx::GLOBAL_CHANNELS && PGX_GLOBAL_OBSTACLES == 0 && PGX_GLOBAL_AGENTS == 1 &&
+                      PGX_GLOBAL_TARGETS == 2 && PGX_GLOBAL_AGENT_IDS == 3 && PGX_GLOBAL_TARGET_IDS == 4,
+                  "codes 0..2 are bits of the kernel's cell bytes, 3 and 4 its id planes");
+    static_assert(PGX_GLOBAL_BAND_CELLS == pgx::GLOBAL_BAND_CELLS && PGX_GLOBAL_BAND_CELLS >= PGX_MAX_SIDE,
+                  "the header publishes the kernel's band, which holds a row of the widest map");
+    uint32_t codes = 0, need = 0;
+    for (int c = 0; c < num_channels; ++c) {
+        const int32_t k = channels[c];
+        if (k < 0 || k >= PGX_NUM_GLOBAL_CHANNELS)
+            return fail_msg(PGX_E_INVALID, "%s: channels[%d] = %d is outside 0..%d", who, c, k, PGX_NUM_GLOBAL_CHANNELS - 1);
+        if (need & (1u << k)) return fail_msg(PGX_E_INVALID, "%s: channels[%d] = %d is given twice", who, c, k);
+        need |= 1u << k;
+        codes |= (uint32_t)k << (4 * c);
+    }
+    if (dtype != PGX_OBS_F32 && dtype != PGX_OBS_U8 && dtype != PGX_OBS_BF16 && dtype != PGX_OBS_F16)
+        return fail_msg(PGX_E_INVALID, "%s: bad dtype %d", who, dtype);
+    if (const int rc = check_aligned(who, "out", out, (size_t)obs_elem_bytes(dtype))) return rc;
+    // an id is index + 1 <= num_agents: uint8 holds 255, bfloat16 every integer up to 256, float16 up to 2048
+    const int32_t limit = dtype == PGX_OBS_U8 ? PGX_GLOBAL_ID_MAX_U8 : dtype == PGX_OBS_BF16 ? PGX_GLOBAL_ID_MAX_BF16 : PGX_MAX_AGENTS;
+    if ((need & 0x18u) && num_agents > limit)
+        return fail_msg(PGX_E_INVALID, "%s: an id channel in %s holds at most %d agents exactly, the env has %d", who,
+                        dtype == PGX_OBS_U8 ? "uint8" : "bfloat16", limit, num_agents);
+    *codes_out = codes;
+    *need_out = need;
+    return PGX_OK;
+}
+}  // namespace
+
+int pgx_global_state_check(int32_t num_agents, const int32_t* channels, int32_t num_channels, int32_t dtype, const void* out) {
+    uint32_t codes = 0, need = 0;
+    return global_state_args(num_agents, channels, num_channels, dtype, out, &codes, &need);
+}
+
+int pgx_global_state(pgx_env* e, const int32_t* channels, int32_t num_channels, int32_t dtype, void* out, void* stream) {
+    static const char who[] = "pgx_global_state";
+    // the argument checks come first and need no device (the handle's agent count is host memory; a NULL handle has none)
+    uint32_t codes = 0, need = 0;
+    if (const int rc = global_state_args(e ? e->cfg.num_agents : 0, channels, num_channels, dtype, out, &codes, &need)) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    pgx::GlobalStateParams p{};
+    static_cast<pgx::StateView&>(p) = state_view(e);   // no cache, no allocation: one launch
+    p.num_channels = num_channels;
+    p.dtype = dtype;
+    p.codes = codes;
+    p.need = need;
+    p.one = dtype == PGX_OBS_F32 ? 0x3F800000u : dtype == PGX_OBS_BF16 ? 0x3F80u : dtype == PGX_OBS_F16 ? 0x3C00u : 1u;
+    p.planes = out;
+    PGX_HIP(pgx::launch_global_state(p, (hipStream_t)stream));
+    return PGX_OK;
+}
+
 int64_t pgx_cost_to_go_builds(pgx_env* e, void* stream) {
     DeviceGuard guard;
     if (const int rc = enter(guard, e, "pgx_cost_to_go_builds", false)) return rc;

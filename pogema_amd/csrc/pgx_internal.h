@@ -350,6 +350,19 @@ struct PolicyInputParams : CostToGoParams {   // without a direction channel onl
 // one: the planes alone, in one launch that reads no field
 hipError_t launch_policy_input(const PolicyInputParams& p, hipStream_t stream);
 
+// ---- global state (pgx_global_state.hip): whole-map planes, chosen, ordered and typed per call -----------------------
+enum { GLOBAL_CHANNELS = 5 };                 // PGX_NUM_GLOBAL_CHANNELS
+enum { GLOBAL_BAND_CELLS = 8192 };            // PGX_GLOBAL_BAND_CELLS: the cells of the band of rows a workgroup holds in LDS
+struct GlobalStateParams : StateView {
+    int32_t num_channels;    // C, 1..GLOBAL_CHANNELS
+    int32_t dtype;           // POLICY_INPUT_* (PGX_OBS_*)
+    uint32_t codes;          // the channel list: PGX_GLOBAL_* of output plane c in bits 4c .. 4c+3
+    uint32_t need;           // bit k set: channel code k is in the list
+    uint32_t one;            // the bit pattern of 1 in `dtype`
+    void* planes;            // [B][C][H][W] of `dtype`
+};
+hipError_t launch_global_state(const GlobalStateParams& p, hipStream_t stream);
+
 // ---- neighbour lists (pgx_neighbours.hip) ---------------------------------------------------------------
 // (not derived from StateView: the kernel reads four of its fields, and this block of 56 bytes is fetched with two loads)
 struct NeighbourParams {

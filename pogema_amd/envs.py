@@ -16,6 +16,7 @@ from typing import Optional
 
 import numpy as np
 
+from ._lib import DEFAULT_GLOBAL_CHANNELS as _DEFAULT_GLOBAL_CHANNELS
 from ._lib import DEFAULT_POLICY_CHANNELS as _DEFAULT_POLICY_CHANNELS
 from .grid_config import GridConfig
 from .vec_env import VecPogema
@@ -197,6 +198,19 @@ class Pogema:
         import torch
         x = self._vec.policy_input(channels=channels, dtype=torch.uint8)[0].cpu().numpy()
         return [x[i] for i in range(x.shape[0])]
+
+    def global_state(self, channels=_DEFAULT_GLOBAL_CHANNELS, dtype=np.uint8):
+        """The whole-map planes a centralised critic reads (VecPogema.global_state) as one numpy array (C, H, W) of
+        `dtype` (float32, float16 or uint8), plane c the channel channels[c]."""
+        import torch
+        table = {np.dtype(np.float32): torch.float32, np.dtype(np.float16): torch.float16, np.dtype(np.uint8): torch.uint8}
+        try:
+            key = np.dtype(dtype)
+        except TypeError:
+            key = None
+        if key not in table:
+            raise ValueError(f"dtype must be one of numpy float32, float16, uint8, got {dtype!r}")
+        return self._vec.global_state(channels=channels, dtype=table[key])[0].cpu().numpy()
 
     def visible_agents(self, k: int = 13):
         """The agents each agent sees in its window (VecPogema.visible_agents): per agent a list of (j, dx, dy) tuples,

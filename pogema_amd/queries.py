@@ -1,6 +1,6 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
-cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes, move outcomes and the
-policy input.  Each is one C-ABI
+cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes, move outcomes, the
+policy input and the global state.  Each is one C-ABI
 call into caller-owned or fresh output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
 from __future__ import annotations
@@ -61,9 +61,39 @@ def parse_channels(channels=_lib.DEFAULT_POLICY_CHANNELS):
     return tuple(codes)
 
 
+def parse_global_channels(channels=_lib.DEFAULT_GLOBAL_CHANNELS):
+    """The channel list of global_state() as a tuple of PGX_GLOBAL_* codes, in the caller's order; the default is the
+    three binary planes.  Anything but a sequence of 1..5 distinct names of _lib.GLOBAL_CHANNELS is a ValueError that names
+    the offending entry and lists the vocabulary.  Needs no engine and no GPU."""
+    table = _lib.GLOBAL_CHANNELS
+    known = f"the channels are {', '.join(repr(n) for n in table)}"
+    if isinstance(channels, (str, bytes)) or not isinstance(channels, (tuple, list)):
+        raise ValueError(f"channels must be a tuple or list of 1..{_lib.NUM_GLOBAL_CHANNELS} channel names, got {channels!r}; {known}")
+    if not 1 <= len(channels) <= _lib.NUM_GLOBAL_CHANNELS:
+        raise ValueError(f"channels must hold 1..{_lib.NUM_GLOBAL_CHANNELS} names, got {len(channels)}; {known}")
+    codes = []
+    for k, name in enumerate(channels):
+        if not isinstance(name, str) or name not in table:
+            raise ValueError(f"channels[{k}] = {name!r} is not a channel; {known}")
+        if table[name] in codes:
+            raise ValueError(f"channels[{k}] = {name!r} is given twice; {known}")
+        codes.append(table[name])
+    return tuple(codes)
+
+
+def check_global_ids(codes, dtype, num_agents):
+    """global_state()'s id-range rule: with an id channel among `codes`, `dtype` must hold every id 1..num_agents
+    exactly -- uint8 up to 255 agents, bfloat16 up to 256; float16 and float32 hold every count the engine accepts.
+    Otherwise a ValueError that names the limit.  Needs no engine and no GPU."""
+    limit = _lib.GLOBAL_ID_MAX.get(_lib.OBS_DTYPES[dtype])
+    if limit is not None and num_agents > limit and any(_lib.GLOBAL_CHANNELS[n] in codes for n in _lib.GLOBAL_ID_CHANNELS):
+        raise ValueError(f"an id channel in {str(dtype).replace('torch.', '')} holds at most {limit} agents exactly, the env "
+                         f"has {num_agents}: use torch.float16 or torch.float32")
+
+
 class QueryMixin:
     """The queries of a VecPogema.  Expects of the class it is mixed into: `_handle`, `_lib`, `device`, `batch`,
-    `num_agents`, `window`, `_ACTION_CODE`, `_prepare_actions()`, `_stream()`."""
+    `num_agents`, `window`, `height`, `width`, `_ACTION_CODE`, `_prepare_actions()`, `_stream()`."""
 
     _SCORE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # PGX_SCORES_* of shield_actions' scores
 
@@ -330,5 +360,35 @@ class QueryMixin:
         shape = (self.batch, self.num_agents, len(codes), self.window, self.window)
         out = query_output("out", out, dtype, shape, self.device)
         _lib.check(self._lib.pgx_policy_input(self._handle, (_lib.C.c_int32 * len(codes))(*codes), len(codes),
+                                              _lib.OBS_DTYPES[dtype], out.data_ptr(), self._stream()))
+        return out
+
+    def global_state(self, channels=_lib.DEFAULT_GLOBAL_CHANNELS, dtype=torch.float32, out=None) -> torch.Tensor:
+        """The global state (docs/SPEC.md S20): [batch, C, H, W] in `dtype`, the whole unpadded map of every env, row x,
+        column y (the orientation of the maps reset() installs, the coordinates of get_state()), plane c the channel
+        channels[c], written once in one launch -- computed on the device from the current state, the state the next
+        step() reads, which this call leaves untouched.  What a centralised critic, a QMIX-style mixer or a central
+        planner reads.
+        `channels`: a tuple or list of 1..5 distinct names, in the order the network wants them:
+            "obstacles"  -- the env's map as it is now (after regeneration, a pool draw or copy_envs()), 0 / 1;
+            "agents"     -- the interior of get_state(occupancy=True)["occupancy"], bit for bit: 1 where an agent stands
+                that is neither hidden nor a `soft` ghost, as in observation plane 1;
+            "targets"    -- 1 on the target cell of every agent whose is_active is set (a ghost's counts, a finished,
+                hidden agent's does not);
+            "agent_ids"  -- i + 1 for the lowest agent i "agents" counts on the cell, else 0;
+            "target_ids" -- j + 1 for the lowest agent j "targets" counts whose target is the cell, else 0 (lifelong
+                targets may coincide).
+        `dtype`: torch.float32, float16, bfloat16 or uint8, chosen per call whatever `obs_dtype` the engine has.  With an
+        id channel it must hold num_agents exactly: uint8 up to 255 agents, bfloat16 up to 256 (ValueError otherwise).
+        One launch that reads no distance field and allocates nothing on the engine side, stream-ordered, no host sync,
+        capturable in a HIP graph from the first call after reset().  `out`: a caller-owned contiguous tensor of that
+        shape and dtype on this device; a 16-byte aligned one is written fastest."""
+        codes = parse_global_channels(channels)
+        if dtype not in _lib.OBS_DTYPES:
+            raise ValueError(f"dtype must be one of torch.float32, torch.float16, torch.bfloat16, torch.uint8, got {dtype!r}")
+        check_global_ids(codes, dtype, self.num_agents)
+        shape = (self.batch, len(codes), self.height, self.width)
+        out = query_output("out", out, dtype, shape, self.device)
+        _lib.check(self._lib.pgx_global_state(self._handle, (_lib.C.c_int32 * len(codes))(*codes), len(codes),
                                               _lib.OBS_DTYPES[dtype], out.data_ptr(), self._stream()))
         return out
