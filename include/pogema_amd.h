@@ -656,6 +656,50 @@ int pgx_policy_input(pgx_env* env, const int32_t* channels, int32_t num_channels
 int pgx_global_state(pgx_env* env, const int32_t* channels, int32_t num_channels, int32_t dtype, void* out, void* stream);
 int pgx_global_state_check(int32_t num_agents, const int32_t* channels, int32_t num_channels, int32_t dtype, const void* out);
 
+/* Agent tokens (docs/SPEC.md S21): the input of a token- or attention-based policy (MAPF-GPT style), one row of
+ * `length` one-byte token ids per agent, written once in one launch -- read from the current device state, the state
+ * the next pgx_step reads, which this call does not change.  With r = obs_radius, W = 2r + 1, S = slots and
+ * L0 = W * W + PGX_TOKEN_SLOT_LEN * S (pgx_agent_tokens_length), the row of agent i of env b is
+ *   an inactive agent (bit 0 of is_active clear): `length` times PGX_TOKEN_PAD;
+ *   entries 0 .. W*W-1: the agent's pgx_cost_to_go window, row-major: PGX_TOKEN_BLOCKED where the window holds -1 or the
+ *       agent's own cell (the window's centre) does, else clamp(cell - centre, -PGX_TOKEN_CLIP, PGX_TOKEN_CLIP) +
+ *       PGX_TOKEN_CLIP;
+ *   entries W*W + 10 s .. W*W + 10 s + 9, slot s: slot 0 is the agent itself with (dx, dy) = (0, 0), slot s >= 1 is
+ *       entry s - 1 of pgx_visible_agents(k = S - 1): agent j at offset (dx, dy).  Ten times PGX_TOKEN_PAD where that
+ *       list has no entry (index -1), else
+ *         +0, +1   dx + PGX_TOKEN_CLIP, dy + PGX_TOKEN_CLIP
+ *         +2, +3   clamp(target of j - position of i, -PGX_TOKEN_CLIP, PGX_TOKEN_CLIP) + PGX_TOKEN_CLIP, per axis
+ *         +4..+8   history[b][j][0..4]: PGX_TOKEN_ACTION0 + v for v in 0..4, PGX_TOKEN_ACTION_NONE for every other
+ *                  value and without a history
+ *         +9       PGX_TOKEN_GREEDY0 + m, m = pgx_goal_directions' PGX_DIRECTIONS_BITS mask at the centre of j's window;
+ *   entries L0 .. length-1: PGX_TOKEN_PAD.
+ * Token ids 0 .. 2 * PGX_TOKEN_CLIP are the integers -PGX_TOKEN_CLIP .. PGX_TOKEN_CLIP; there are PGX_NUM_TOKENS ids.
+ *   slots    1..PGX_MAX_TOKEN_SLOTS, the agent included
+ *   length   L0..PGX_MAX_TOKEN_LENGTH
+ *   flags    must be 0
+ *   history  device buffer int8 [batch, num_agents, PGX_TOKEN_HISTORY], most recent action first, or NULL; only read
+ *   tokens   device buffer uint8 [batch, num_agents, length], must not be NULL; any alignment works, rows whose bytes
+ *            fill whole 16-byte lines of the buffer are written with 16-byte stores
+ * Shares pgx_cost_to_go's cache: stale fields are rebuilt first (pgx_cost_to_go_builds counts them), and the first call
+ * of any entry point that uses the cache allocates it -- PGX_E_STATE inside a graph capture; later calls are asynchronous
+ * on `stream`, need no host sync and can be captured.  PGX_E_INVALID for slots, length or flags outside their ranges or
+ * a NULL `tokens` (checked before the device is touched); PGX_E_STATE before the first reset, like pgx_step.
+ * pgx_agent_tokens_length needs no handle: W * W + PGX_TOKEN_SLOT_LEN * slots, -1 for an obs_radius outside
+ * 1..PGX_MAX_OBS_RADIUS or slots outside 1..PGX_MAX_TOKEN_SLOTS. */
+#define PGX_TOKEN_CLIP 20
+#define PGX_TOKEN_BLOCKED 41
+#define PGX_TOKEN_ACTION_NONE 42
+#define PGX_TOKEN_ACTION0 43
+#define PGX_TOKEN_GREEDY0 48
+#define PGX_TOKEN_PAD 64
+#define PGX_NUM_TOKENS 65
+#define PGX_TOKEN_HISTORY 5
+#define PGX_TOKEN_SLOT_LEN 10
+#define PGX_MAX_TOKEN_SLOTS 32
+#define PGX_MAX_TOKEN_LENGTH 2048
+int pgx_agent_tokens(pgx_env* env, int32_t slots, int32_t length, int32_t flags, const int8_t* history, uint8_t* tokens, void* stream);
+int64_t pgx_agent_tokens_length(int32_t obs_radius, int32_t slots);
+
 /* Number of out-of-range actions (outside 0..4) that ACTIVE agents submitted since the last call (bad_action =
  * PGX_BAD_ACTION_FLAG only; otherwise always 0).  Inactive agents' actions are never looked at, as in the reference's
  * `if self.grid.is_active[agent_idx]` guards.  Synchronises `stream`, then clears the counter.  The host side turns a

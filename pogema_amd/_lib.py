@@ -77,6 +77,21 @@ GLOBAL_ID_CHANNELS = ("agent_ids", "target_ids")
 GLOBAL_ID_MAX = {1: 255, 2: 256}
 # PGX_GLOBAL_BAND_CELLS: a workgroup of pgx_global_state holds GLOBAL_BAND_CELLS // W whole rows of a map at a time
 GLOBAL_BAND_CELLS = 8192
+# PGX_TOKEN_* / PGX_*_TOKEN_*: the vocabulary and the limits of pgx_agent_tokens (docs/SPEC.md S21)
+TOKEN_CLIP = 20            # ids 0 .. 2 * TOKEN_CLIP are the integers -TOKEN_CLIP .. TOKEN_CLIP
+TOKEN_BLOCKED = 41
+TOKEN_ACTION_NONE = 42
+TOKEN_ACTION0 = 43         # .. + 4: a recorded action 0..4
+TOKEN_GREEDY0 = 48         # .. + 15: the greedy-move mask
+TOKEN_PAD = 64
+NUM_TOKENS = 65
+TOKEN_HISTORY = 5          # recorded actions per agent
+TOKEN_SLOT_LEN = 10        # entries per agent slot
+MAX_TOKEN_SLOTS = 32
+MAX_TOKEN_LENGTH = 2048
+TOKENS = {"CLIP": TOKEN_CLIP, "BLOCKED": TOKEN_BLOCKED, "ACTION_NONE": TOKEN_ACTION_NONE, "ACTION0": TOKEN_ACTION0,
+          "GREEDY0": TOKEN_GREEDY0, "PAD": TOKEN_PAD, "NUM_TOKENS": NUM_TOKENS, "HISTORY": TOKEN_HISTORY,
+          "SLOT_LEN": TOKEN_SLOT_LEN, "MAX_SLOTS": MAX_TOKEN_SLOTS, "MAX_LENGTH": MAX_TOKEN_LENGTH}
 
 
 # every symbol include/pogema_amd.h declares; tests/test_abi.py checks the library exports them all
@@ -90,6 +105,7 @@ EXPORTED_SYMBOLS = (
     "pgx_cost_to_go", "pgx_cost_to_go_bytes", "pgx_cost_to_go_builds", "pgx_visible_agents", "pgx_pibt_actions",
     "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan", "pgx_move_outcomes",
     "pgx_policy_input", "pgx_copy_envs", "pgx_global_state", "pgx_global_state_check",
+    "pgx_agent_tokens", "pgx_agent_tokens_length",
 )
 
 
@@ -223,6 +239,10 @@ def load() -> C.CDLL:
     lib.pgx_global_state.restype = C.c_int
     lib.pgx_global_state_check.argtypes = [i32, C.POINTER(i32), i32, i32, vp]
     lib.pgx_global_state_check.restype = C.c_int
+    lib.pgx_agent_tokens.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    lib.pgx_agent_tokens.restype = C.c_int
+    lib.pgx_agent_tokens_length.argtypes = [i32, i32]
+    lib.pgx_agent_tokens_length.restype = i64
     lib.pgx_copy_envs.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.pgx_copy_envs.restype = C.c_int
     lib.pgx_set_map_pool.argtypes = [vp, vp, i32, vp, vp]

@@ -1093,7 +1093,7 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
 
 // The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
 // first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_goal_directions,
-// pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE, pgx_policy_input with a direction channel).  `who` names that entry point in the error messages.
+// pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE, pgx_policy_input with a direction channel, pgx_agent_tokens).  `who` names that entry point in the error messages.
 static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p) {
     const pgx_config& c = e->cfg;
     const pgx::CostToGoLayout l = pgx::cost_to_go_layout(c.batch, c.num_agents, c.height, c.width);
@@ -1296,6 +1296,45 @@ int pgx_goal_directions(pgx_env* e, int32_t flags, void* out, int32_t format, vo
     pgx::CostToGoParams p{};
     if (const int rc = cost_to_go_cache(e, s, who, &p)) return rc;
     PGX_HIP(pgx::launch_goal_directions(p, out, format, s));
+    return PGX_OK;
+}
+
+// ---- agent tokens (docs/SPEC.md S21) ------------------------------------------------------------------------
+int64_t pgx_agent_tokens_length(int32_t obs_radius, int32_t slots) {
+    static const char who[] = "pgx_agent_tokens_length";
+    if (obs_radius < 1 || obs_radius > PGX_MAX_OBS_RADIUS)
+        return fail_msg(PGX_E_INVALID, "%s: obs_radius %d is outside 1..%d", who, obs_radius, PGX_MAX_OBS_RADIUS);
+    if (slots < 1 || slots > PGX_MAX_TOKEN_SLOTS)
+        return fail_msg(PGX_E_INVALID, "%s: slots %d is outside 1..%d", who, slots, PGX_MAX_TOKEN_SLOTS);
+    const int64_t w = 2 * (int64_t)obs_radius + 1;
+    return w * w + (int64_t)PGX_TOKEN_SLOT_LEN * slots;
+}
+
+int pgx_agent_tokens(pgx_env* e, int32_t slots, int32_t length, int32_t flags, const int8_t* history, uint8_t* tokens,
+                     void* stream) {
+    static const char who[] = "pgx_agent_tokens";
+    // the argument checks come first and need no device (the handle's radius is host memory)
+    if (!e) return fail_msg(PGX_E_INVALID, "%s: null handle", who);
+    if (!tokens) return fail_msg(PGX_E_INVALID, "%s: tokens is null", who);
+    if (const int rc = check_flags(who, flags, 0)) return rc;
+    if (slots < 1 || slots > PGX_MAX_TOKEN_SLOTS)
+        return fail_msg(PGX_E_INVALID, "%s: slots %d is outside 1..%d", who, slots, PGX_MAX_TOKEN_SLOTS);
+    const int64_t l0 = pgx_agent_tokens_length(e->cfg.obs_radius, slots);
+    static_assert((2 * PGX_MAX_OBS_RADIUS + 1) * (2 * PGX_MAX_OBS_RADIUS + 1) + PGX_TOKEN_SLOT_LEN * PGX_MAX_TOKEN_SLOTS <=
+                      PGX_MAX_TOKEN_LENGTH, "the longest row fits the largest length");
+    if (length < l0 || length > PGX_MAX_TOKEN_LENGTH)
+        return fail_msg(PGX_E_INVALID, "%s: length %d is outside %lld..%d (obs_radius %d, %d slots)", who, length, (long long)l0,
+                        PGX_MAX_TOKEN_LENGTH, e->cfg.obs_radius, slots);
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::TokenParams p{};
+    if (const int rc = cost_to_go_cache(e, s, who, &p)) return rc;  // (fills the CostToGoParams base of p)
+    p.slots = slots;
+    p.length = length;
+    p.history = history;
+    p.tokens = tokens;
+    PGX_HIP(pgx::launch_agent_tokens(p, s));
     return PGX_OK;
 }
 

@@ -335,6 +335,16 @@ enum { DIRECTIONS_F32 = 0, DIRECTIONS_U8 = 1, DIRECTIONS_BITS = 2 };  // PGX_DIR
 // [B][A][4][2r+1][2r+1] float32 or u8, or [B][A][2r+1][2r+1] u8 masks
 hipError_t launch_goal_directions(const CostToGoParams& p, void* out, int format, hipStream_t stream);
 
+// ---- agent tokens (pgx_agent_tokens.hip): one row of token ids per agent (docs/SPEC.md S21) -------------------------
+struct TokenParams : CostToGoParams {   // `out` is not used
+    int32_t slots;           // S, 1..PGX_MAX_TOKEN_SLOTS: the agent itself and S - 1 neighbours
+    int32_t length;          // bytes per row, W * W + 10 * S .. PGX_MAX_TOKEN_LENGTH
+    const int8_t* history;   // [B][A][5] recorded actions, most recent first; may be null
+    uint8_t* tokens;         // [B][A][length]
+};
+// the refresh of the cost-to-go cache `p` describes, then the rows of every agent in one launch
+hipError_t launch_agent_tokens(const TokenParams& p, hipStream_t stream);
+
 // ---- policy input (pgx_policy_input.hip): the network's window planes, chosen, ordered and typed per call ------------
 enum { POLICY_INPUT_F32 = 0, POLICY_INPUT_U8 = 1, POLICY_INPUT_BF16 = 2, POLICY_INPUT_F16 = 3 };  // PGX_OBS_* (include/pogema_amd.h)
 enum { POLICY_CHANNELS = 8 };                                                                     // PGX_NUM_CHANNELS

@@ -212,6 +212,16 @@ class Pogema:
             raise ValueError(f"dtype must be one of numpy float32, float16, uint8, got {dtype!r}")
         return self._vec.global_state(channels=channels, dtype=table[key])[0].cpu().numpy()
 
+    def agent_tokens(self, slots: int = 13, history=None, length=None):
+        """The token observations of every agent (VecPogema.agent_tokens) as one numpy uint8 array (agents, length).
+        `history`: five recorded actions per agent, most recent first, as an integer array (agents, 5), None = nothing
+        recorded."""
+        import torch
+        vec = self._vec
+        if history is not None:
+            history = torch.as_tensor(np.asarray(history, dtype=np.int8)[None], device=vec.device)
+        return vec.agent_tokens(slots=slots, history=history, length=length)[0].cpu().numpy()
+
     def visible_agents(self, k: int = 13):
         """The agents each agent sees in its window (VecPogema.visible_agents): per agent a list of (j, dx, dy) tuples,
         nearest first, truncated to `k`."""

@@ -1,6 +1,6 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
 cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes, move outcomes, the
-policy input and the global state.  Each is one C-ABI
+policy input, the global state and the agent tokens.  Each is one C-ABI
 call into caller-owned or fresh output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
 from __future__ import annotations
@@ -138,7 +138,7 @@ class QueryMixin:
 
     @property
     def cost_to_go_builds(self) -> int:
-        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), goal_directions() and
+        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), goal_directions(), agent_tokens() and
         shield_actions(tie_break="distance") have built since this env was created (synchronises the stream)."""
         n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
         if n < 0:
@@ -391,4 +391,54 @@ class QueryMixin:
         out = query_output("out", out, dtype, shape, self.device)
         _lib.check(self._lib.pgx_global_state(self._handle, (_lib.C.c_int32 * len(codes))(*codes), len(codes),
                                               _lib.OBS_DTYPES[dtype], out.data_ptr(), self._stream()))
+        return out
+
+    def _token_history(self, history):
+        """agent_tokens()' `history` argument as a contiguous int8 tensor [batch, agents, 5] on this device, or None."""
+        if history is None:
+            return None
+        shape = (self.batch, self.num_agents, _lib.TOKEN_HISTORY)
+        if not isinstance(history, torch.Tensor):
+            raise TypeError(f"history must be a torch.Tensor or None, got {type(history).__name__}")
+        if history.dtype != torch.int8:
+            raise TypeError(f"history must be an int8 tensor, got {history.dtype}")
+        if tuple(history.shape) != shape or history.device != self.device:
+            raise ValueError(f"history must have shape {shape} on {self.device}")
+        return history.contiguous()
+
+    def agent_tokens(self, slots: int = 13, history=None, length=None, out=None) -> torch.Tensor:
+        """Token observations (docs/SPEC.md S21), the input of MAPF-GPT-style policies: uint8 [batch, agents, length],
+        one row of token ids (pogema_amd.TOKENS) per agent, written once in one launch -- computed on the device from
+        the current state, the state the next step() reads, which this call leaves untouched.  With W = 2 * obs_radius
+        + 1 and L0 = W * W + 10 * slots (pogema_amd.token_length), the row of an active agent i is
+            entries 0 .. W*W-1: its cost_to_go() window relative to its own cost, row-major: BLOCKED where cost_to_go()
+                gives -1 there or at the centre, else clamp(cost - own, -20, 20) + 20;
+            ten entries per slot: slot 0 the agent itself, slot s >= 1 entry s - 1 of visible_agents(k=slots - 1) --
+                dx + 20, dy + 20; the listed agent's target minus i's position, clamped to -20..20, + 20 per axis; the
+                listed agent's five `history` values (43 + v for an action v in 0..4, ACTION_NONE for anything else);
+                48 + its greedy-move mask, goal_directions("bits") at its own window centre.  Ten PAD where the list
+                has no entry;
+            entries L0 .. length-1: PAD.
+        An inactive agent's row is all PAD.  obs_radius=5, slots=13, length=256 is MAPF-GPT's 121 + 130 + 5 context.
+        `slots`: 1..32, the agent included.  `length`: L0..2048, None = L0.  `history`: an int8 tensor [batch, agents, 5]
+        on this device, most recent action first (TokenHistory keeps one; made contiguous if it is not), None = nothing
+        recorded.
+        Shares cost_to_go()'s cache under goal_directions()' rules: stale fields are rebuilt first, whichever call is
+        first allocates the cache (not inside a graph capture); later calls are stream-ordered, need no host sync and can
+        be captured.  `out`: a caller-owned contiguous uint8 tensor of that shape on this device, at any alignment."""
+        if isinstance(slots, bool) or not isinstance(slots, (int, np.integer)) or not 1 <= slots <= _lib.MAX_TOKEN_SLOTS:
+            raise ValueError(f"slots must be an integer in 1..{_lib.MAX_TOKEN_SLOTS}, got {slots!r}")
+        slots = int(slots)
+        l0 = self.window * self.window + _lib.TOKEN_SLOT_LEN * slots
+        if length is None:
+            length = l0
+        if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or not l0 <= length <= _lib.MAX_TOKEN_LENGTH:
+            raise ValueError(f"length must be an integer in {l0}..{_lib.MAX_TOKEN_LENGTH} (L0 = {l0} for this window and "
+                             f"{slots} slots), got {length!r}")
+        length = int(length)
+        history = self._token_history(history)
+        out = query_output("out", out, torch.uint8, (self.batch, self.num_agents, length), self.device)
+        _lib.check(self._lib.pgx_agent_tokens(self._handle, slots, length, 0,
+                                              history.data_ptr() if history is not None else None, out.data_ptr(),
+                                              self._stream()))
         return out
