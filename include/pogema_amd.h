@@ -574,6 +574,41 @@ int pgx_move_outcomes(pgx_env* env, const void* actions, int32_t action_dtype, i
 #define PGX_DIRECTIONS_BITS 2
 int pgx_goal_directions(pgx_env* env, int32_t flags, void* out, int32_t format, void* stream);
 
+/* Path-to-goal planes and sub-goals (docs/SPEC.md S22), the input and the reward signal of planning-plus-learning
+ * policies ("Learn to Follow" style), read from the current device state -- the state the next pgx_step reads, which
+ * this call does not change.  With r = obs_radius, W = 2r + 1 and D the agent's distance field (pgx_cost_to_go's), the
+ * PATH of an agent at cell p0 is p0, p1, ...: p(k+1) = p(k) + MOVES[a] for the lowest a of 1..4 (up, down, left, right)
+ * whose destination has a defined distance strictly smaller than p(k)'s -- the lowest plane pgx_goal_directions sets
+ * at p(k), so p1 is the cell pgx_expert_actions moves to.  The MARKED PREFIX p1..pn ends at the first of: p(n) is the
+ * target; p(n+1) lies outside the agent's W x W window (nothing after it is marked, even if the path re-enters);
+ * n = the cap.  n <= W * W - 1 whatever the field holds.  n = 0 for an agent that is not active (bit 0 of is_active
+ * clear; its field is not read), stands on its target or has no path to it: zero planes, sub-goal (0, 0), length 0.
+ *   flags    reserved, must be 0
+ *   steps    0: no cap; 1..PGX_MAX_PATH_STEPS: the cap (one above W * W - 1 behaves like 0)
+ *   format   of `planes`, checked even when `planes` is NULL:
+ *            PGX_PATHS_F32   f32 [batch, agents, W, W]  1.0 at window cell (u, v) iff it is one of p1..pn, else 0.0
+ *                            (4-byte aligned); the orientation of observation plane 0; the centre is never marked
+ *            PGX_PATHS_U8    u8  [batch, agents, W, W]  1 / 0
+ *            PGX_PATHS_ROWS  i32 [batch, agents, W]     bit v of word u = cell (u, v); bit 31 is never set (4-byte aligned)
+ *   planes   device buffer of `format`, or NULL: no plane is written at all.  A 16-byte aligned `planes` is written
+ *            with 16-byte stores, any other with one store per element.
+ *   subgoal  device i8 [batch, agents, 2], or NULL: the offset (dx, dy) of p(n) from p0 in pgx_visible_agents' convention
+ *   length   device i32 [batch, agents], 4-byte aligned, or NULL: n.  n <= the centre of pgx_cost_to_go's window, with
+ *            equality iff the prefix ended on the target.
+ * Shares pgx_cost_to_go's distance-field cache exactly as pgx_goal_directions does: the call refreshes it (stale fields
+ * are rebuilt and counted by pgx_cost_to_go_builds) and then walks in one more launch; whichever entry point uses the
+ * cache first allocates it -- inside a graph capture that first call returns PGX_E_STATE, a failed allocation
+ * PGX_E_NOMEM / PGX_E_HIP naming the bytes.  Afterwards asynchronous on `stream`, no host sync, capturable in a HIP
+ * graph.  PGX_E_INVALID when all three outputs are NULL, for non-zero flags, an unknown format, steps outside
+ * 0..PGX_MAX_PATH_STEPS, a misaligned float32 or rows `planes` or a misaligned `length` (checked before the handle: no
+ * device needed); PGX_E_STATE before the first reset, like pgx_step. */
+#define PGX_PATHS_F32 0
+#define PGX_PATHS_U8 1
+#define PGX_PATHS_ROWS 2
+#define PGX_MAX_PATH_STEPS 960
+int pgx_goal_paths(pgx_env* env, int32_t flags, int32_t steps, int32_t format, void* planes, int8_t* subgoal,
+                   int32_t* length, void* stream);
+
 /* Policy input (docs/SPEC.md S18): the stack of binary window planes a learnt MAPF policy reads, written once, in the
  * order and the number format the network takes -- read from the current device state, the state the next pgx_step
  * reads, which this call does not change.  Plane c of every agent's window is the channel channels[c]:

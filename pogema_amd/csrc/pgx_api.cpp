@@ -1093,7 +1093,7 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
 
 // The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
 // first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_goal_directions,
-// pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE, pgx_policy_input with a direction channel, pgx_agent_tokens).  `who` names that entry point in the error messages.
+// pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE, pgx_policy_input with a direction channel, pgx_agent_tokens, pgx_goal_paths).  `who` names that entry point in the error messages.
 static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p) {
     const pgx_config& c = e->cfg;
     const pgx::CostToGoLayout l = pgx::cost_to_go_layout(c.batch, c.num_agents, c.height, c.width);
@@ -1296,6 +1296,40 @@ int pgx_goal_directions(pgx_env* e, int32_t flags, void* out, int32_t format, vo
     pgx::CostToGoParams p{};
     if (const int rc = cost_to_go_cache(e, s, who, &p)) return rc;
     PGX_HIP(pgx::launch_goal_directions(p, out, format, s));
+    return PGX_OK;
+}
+
+// ---- path-to-goal planes and sub-goals (docs/SPEC.md S22) -------------------------------------------------
+int pgx_goal_paths(pgx_env* e, int32_t flags, int32_t steps, int32_t format, void* planes, int8_t* subgoal, int32_t* length,
+                   void* stream) {
+    static const char who[] = "pgx_goal_paths";
+    // the argument checks come first and need no device
+    if (!planes && !subgoal && !length)
+        return fail_msg(PGX_E_INVALID, "%s: planes, subgoal and length are all null", who);
+    if (const int rc = check_flags(who, flags, 0)) return rc;
+    static_assert(PGX_PATHS_F32 == pgx::PATHS_F32 && PGX_PATHS_U8 == pgx::PATHS_U8 && PGX_PATHS_ROWS == pgx::PATHS_ROWS,
+                  "the kernels' format codes are the header's");
+    if (format != PGX_PATHS_F32 && format != PGX_PATHS_U8 && format != PGX_PATHS_ROWS)
+        return fail_msg(PGX_E_INVALID, "%s: bad format %d", who, format);
+    static_assert(PGX_MAX_PATH_STEPS == (2 * PGX_MAX_OBS_RADIUS + 1) * (2 * PGX_MAX_OBS_RADIUS + 1) - 1,
+                  "the largest window's cells but the centre");
+    if (steps < 0 || steps > PGX_MAX_PATH_STEPS)
+        return fail_msg(PGX_E_INVALID, "%s: steps %d is outside 0..%d (0: no cap)", who, steps, PGX_MAX_PATH_STEPS);
+    if (format != PGX_PATHS_U8)
+        if (const int rc = check_aligned(who, format == PGX_PATHS_F32 ? "a float32 planes" : "a rows planes", planes, 4)) return rc;
+    if (const int rc = check_aligned(who, "length", length, 4)) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::GoalPathParams p{};
+    if (const int rc = cost_to_go_cache(e, s, who, &p)) return rc;  // (fills the CostToGoParams base of p)
+    const int32_t w = 2 * e->cfg.obs_radius + 1;
+    p.format = format;
+    p.cap = steps == 0 || steps > w * w - 1 ? w * w - 1 : steps;   // the walk's trip count: no field can exceed it
+    p.planes = planes;
+    p.subgoal = subgoal;
+    p.length = length;
+    PGX_HIP(pgx::launch_goal_paths(p, s));
     return PGX_OK;
 }
 

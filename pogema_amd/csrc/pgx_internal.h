@@ -335,6 +335,18 @@ enum { DIRECTIONS_F32 = 0, DIRECTIONS_U8 = 1, DIRECTIONS_BITS = 2 };  // PGX_DIR
 // [B][A][4][2r+1][2r+1] float32 or u8, or [B][A][2r+1][2r+1] u8 masks
 hipError_t launch_goal_directions(const CostToGoParams& p, void* out, int format, hipStream_t stream);
 
+// ---- path-to-goal planes and sub-goals (pgx_goal_paths.hip, docs/SPEC.md S22) -------------------------------
+enum { PATHS_F32 = 0, PATHS_U8 = 1, PATHS_ROWS = 2 };  // PGX_PATHS_* (include/pogema_amd.h)
+struct GoalPathParams : CostToGoParams {   // `out` is not used
+    int32_t format;          // PATHS_*: the elements of `planes`
+    int32_t cap;             // most cells marked per agent, 1..(2r+1)^2 - 1: the walk's trip count, whatever a field holds
+    void* planes;            // [B][A][2r+1][2r+1] float32 or u8, or [B][A][2r+1] i32 row masks; may be null
+    int8_t* subgoal;         // [B][A][2] offset (dx, dy) of the last marked cell; may be null
+    int32_t* length;         // [B][A] cells marked; may be null
+};
+// the refresh of the cost-to-go cache `p` describes, then the paths of every agent in one launch
+hipError_t launch_goal_paths(const GoalPathParams& p, hipStream_t stream);
+
 // ---- agent tokens (pgx_agent_tokens.hip): one row of token ids per agent (docs/SPEC.md S21) -------------------------
 struct TokenParams : CostToGoParams {   // `out` is not used
     int32_t slots;           // S, 1..PGX_MAX_TOKEN_SLOTS: the agent itself and S - 1 neighbours

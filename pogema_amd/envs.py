@@ -192,6 +192,12 @@ class Pogema:
         d = self._vec.goal_directions(format="uint8")[0].cpu().numpy()
         return [d[i] for i in range(d.shape[0])]
 
+    def goal_paths(self, steps=None):
+        """The path to the goal of every agent (VecPogema.goal_paths) as a list of (plane uint8 (W, W), (dx, dy), length)
+        tuples: the marked window cells, the sub-goal's offset and the number of marked cells."""
+        planes, subgoal, length = (t[0].cpu().numpy() for t in self._vec.goal_paths(steps=steps, format="uint8"))
+        return [(planes[i], (int(subgoal[i][0]), int(subgoal[i][1])), int(length[i])) for i in range(planes.shape[0])]
+
     def policy_input(self, channels=_DEFAULT_POLICY_CHANNELS):
         """The network's input planes of every agent (VecPogema.policy_input) as a list of uint8 (C, W, W) numpy
         arrays, plane c the channel channels[c]."""

@@ -1,6 +1,6 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
-cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes, move outcomes, the
-policy input, the global state and the agent tokens.  Each is one C-ABI
+cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes, path-to-goal planes,
+move outcomes, the policy input, the global state and the agent tokens.  Each is one C-ABI
 call into caller-owned or fresh output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
 from __future__ import annotations
@@ -138,7 +138,7 @@ class QueryMixin:
 
     @property
     def cost_to_go_builds(self) -> int:
-        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), goal_directions(), agent_tokens() and
+        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), goal_directions(), goal_paths(), agent_tokens() and
         shield_actions(tie_break="distance") have built since this env was created (synchronises the stream)."""
         n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
         if n < 0:
@@ -307,6 +307,50 @@ class QueryMixin:
         _lib.check(self._lib.pgx_goal_directions(self._handle, 0, out.data_ptr(), _lib.DIRECTIONS_FORMATS[format],
                                                  self._stream()))
         return out
+
+    def goal_paths(self, steps=None, format: str = "float32", planes: bool = True, out=None):
+        """Path-to-goal planes and sub-goals (docs/SPEC.md S22), the input and the reward signal of planning-plus-learning
+        policies ("Learn to Follow" style), computed on the device from the current state -- the state the next step()
+        reads, which this call leaves untouched.  An agent's path descends its distance field from its own cell: at
+        every cell the lowest of the moves 1..4 (up, down, left, right) that leads to a cell strictly closer to the
+        target -- the lowest plane goal_directions() sets there, so its first cell is the one expert_actions() moves to.
+        The cells p1..pn are marked until the target is reached, the next cell would leave the agent's window (nothing
+        after it is marked, even if the path re-enters) or n = `steps`.  Returns
+            (planes [batch, agents, W, W] (W = 2 * obs_radius + 1, the orientation of observation plane 0): 1 on the
+                 marked cells; the centre is never marked, the target is when reached.  None with `planes=False`;
+             subgoal int8 [batch, agents, 2]: the offset (dx, dy) of the last marked cell from the agent, in
+                 visible_agents()' convention;
+             length int32 [batch, agents]: n; at most cost_to_go()'s centre value, equal iff the path ended on the target).
+        An agent that is inactive, stands on its target or has no path to it gets zero planes, (0, 0) and 0.
+        `steps`: None = no cap, or an integer in 1..MAX_PATH_STEPS (960).
+        `format`: "float32" -> float32 [batch, agents, W, W] of 0.0 / 1.0;
+                  "uint8"   -> uint8 [batch, agents, W, W] of 0 / 1;
+                  "rows"    -> int32 [batch, agents, W], bit v of word u = cell (u, v).
+        `planes=False` writes no planes at all: the sub-goals and lengths alone.
+        Shares cost_to_go()'s cache under goal_directions()' rules: stale fields are rebuilt first, whichever call is
+        first allocates the cache (not inside a graph capture); later calls are stream-ordered, need no host sync and can
+        be captured.  `out=(planes, subgoal, length)`, with `planes=False` `out=(subgoal, length)`: caller-owned
+        contiguous tensors of those dtypes and shapes on this device; a 16-byte aligned `planes` is written fastest."""
+        B, A, W = self.batch, self.num_agents, self.window
+        if format not in _lib.PATHS_FORMATS:
+            raise ValueError(f"format must be one of {sorted(_lib.PATHS_FORMATS)}, got {format!r}")
+        if steps is not None and (isinstance(steps, bool) or not isinstance(steps, (int, np.integer))
+                                  or not 1 <= steps <= _lib.MAX_PATH_STEPS):
+            raise ValueError(f"steps must be None or an integer in 1..{_lib.MAX_PATH_STEPS}, got {steps!r}")
+        if planes:
+            plane_out, subgoal, length = _split(out, ("planes", "subgoal", "length"))
+            dtype = {"float32": torch.float32, "uint8": torch.uint8, "rows": torch.int32}[format]
+            shape = (B, A, W) if format == "rows" else (B, A, W, W)
+            plane_out = query_output("out[planes]", plane_out, dtype, shape, self.device)
+        else:
+            plane_out = None
+            subgoal, length = _split(out, ("subgoal", "length"))
+        subgoal = query_output("out[subgoal]", subgoal, torch.int8, (B, A, 2), self.device)
+        length = query_output("out[length]", length, torch.int32, (B, A), self.device)
+        _lib.check(self._lib.pgx_goal_paths(self._handle, 0, 0 if steps is None else int(steps), _lib.PATHS_FORMATS[format],
+                                            plane_out.data_ptr() if plane_out is not None else None, subgoal.data_ptr(),
+                                            length.data_ptr(), self._stream()))
+        return plane_out, subgoal, length
 
     def move_outcomes(self, actions, out=None):
         """Move outcomes (docs/SPEC.md S17): what the move phase of step(actions) would do to every agent and why a move
