@@ -444,6 +444,24 @@ int pgx_visible_agents(pgx_env* env, int32_t k, int32_t flags, int32_t* index, i
 int pgx_pibt_actions(pgx_env* env, int32_t flags, const int32_t* priority, void* actions, int32_t action_dtype,
                      int32_t* next_xy, void* stream);
 
+/* Cooperative one-step planner with the swap operation (docs/SPEC.md S23): pgx_pibt_actions' planner -- the same planned
+ * agents, candidate cells, order of the candidates, serving order, reservations and outputs -- plus the rule that lets
+ * two agents change places in a corridor or a dead end.  An agent whose best cell leads into a corridor it cannot pass
+ * while another agent has to come out of it (decided by two walks along the corridor, from the state alone) tries its
+ * candidates BACK TO FRONT, and when its first-tried candidate holds, the other agent (its partner) is pulled into the
+ * cell it leaves.  A walk takes at most PGX_SWAP_MAX_WALK steps; a longer corridor counts as "no swap" -- the cap is part
+ * of the semantics.  Every guarantee of pgx_pibt_actions holds: no two planned agents share a next cell, no two swap
+ * cells, and under PGX_COLLISION_SOFT a pgx_step with these actions puts every planned agent on its next cell.  A
+ * heuristic: it solves corridor and dead-end instances the plain planner livelocks on and loses a few the plain planner
+ * solves, which is why it is an entry point of its own.
+ *   flags     reserved, must be 0
+ *   priority, actions, action_dtype, next_xy   as in pgx_pibt_actions
+ * Cache, allocation, capture, status codes and the order of the checks (arguments before the handle: no device needed)
+ * are pgx_pibt_actions': the call refreshes pgx_cost_to_go's distance-field cache and then plans in one more launch. */
+#define PGX_SWAP_MAX_WALK 2048
+int pgx_pibt_swap_actions(pgx_env* env, int32_t flags, const int32_t* priority, void* actions, int32_t action_dtype,
+                          int32_t* next_xy, void* stream);
+
 /* Multi-step planner (docs/SPEC.md S16): pgx_pibt_actions' planner iterated `horizon` times inside one launch, on a
  * private copy of the positions -- the call reads the current device state and changes none of it.  The targets and
  * their distance fields are held for the whole lookahead.  Step h plans from the cells step h - 1 sent the agents to;

@@ -61,6 +61,7 @@ MAX_PATH_STEPS = 960  # PGX_MAX_PATH_STEPS: the largest cap of pgx_goal_paths, 3
 SHIELD_TIE_BREAKS = {None: 0, "distance": 1}  # flags of pgx_shield_actions (PGX_SHIELD_TIE_DISTANCE)
 MAX_PLAN_HORIZON = 256  # PGX_MAX_PLAN_HORIZON: steps of one pgx_pibt_plan
 PLAN_FIXED_PRIORITY = 1  # PGX_PLAN_FIXED_PRIORITY: flag of pgx_pibt_plan
+SWAP_MAX_WALK = 2048  # PGX_SWAP_MAX_WALK: steps of a corridor walk of pgx_pibt_swap_actions (docs/SPEC.md S23)
 # PGX_OUTCOME_*: the codes of pgx_move_outcomes, index = code (docs/SPEC.md S17)
 OUTCOMES = ("STAY", "MOVED", "OBSTACLE", "SWAP", "OCCUPIED", "FOLLOW", "CONTESTED")
 NUM_OUTCOMES = len(OUTCOMES)  # PGX_NUM_OUTCOMES
@@ -107,7 +108,7 @@ EXPORTED_SYMBOLS = (
     "pgx_cost_to_go", "pgx_cost_to_go_bytes", "pgx_cost_to_go_builds", "pgx_visible_agents", "pgx_pibt_actions",
     "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan", "pgx_move_outcomes",
     "pgx_policy_input", "pgx_copy_envs", "pgx_global_state", "pgx_global_state_check",
-    "pgx_agent_tokens", "pgx_agent_tokens_length", "pgx_goal_paths",
+    "pgx_agent_tokens", "pgx_agent_tokens_length", "pgx_goal_paths", "pgx_pibt_swap_actions",
 )
 
 
@@ -227,6 +228,8 @@ def load() -> C.CDLL:
     lib.pgx_visible_agents.restype = C.c_int
     lib.pgx_pibt_actions.argtypes = [vp, i32, vp, vp, i32, vp, vp]
     lib.pgx_pibt_actions.restype = C.c_int
+    lib.pgx_pibt_swap_actions.argtypes = [vp, i32, vp, vp, i32, vp, vp]
+    lib.pgx_pibt_swap_actions.restype = C.c_int
     lib.pgx_pibt_plan.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.pgx_pibt_plan.restype = C.c_int
     lib.pgx_goal_directions.argtypes = [vp, i32, vp, i32, vp]

@@ -1164,6 +1164,36 @@ int pgx_pibt_actions(pgx_env* e, int32_t flags, const int32_t* priority, void* a
     return PGX_OK;
 }
 
+// ---- cooperative planner with the swap operation (docs/SPEC.md S23) ----------------------------------------
+int pgx_pibt_swap_actions(pgx_env* e, int32_t flags, const int32_t* priority, void* actions, int32_t action_dtype,
+                          int32_t* next_xy, void* stream) {
+    static const char who[] = "pgx_pibt_swap_actions";
+    static_assert(PGX_SWAP_MAX_WALK == pgx::SWAP_MAX_WALK, "the header's walk cap is the kernel's");
+    // the argument checks come first and need no device
+    if (!actions) return fail_msg(PGX_E_INVALID, "%s: actions is null", who);
+    if (const int rc = check_flags(who, flags, 0)) return rc;
+    if (const int rc = check_action_dtype(who, action_dtype)) return rc;
+    static const size_t action_bytes[3] = {1, 4, 8};
+    if (const int rc = check_aligned(who, "actions", actions, action_bytes[action_dtype])) return rc;
+    if (const int rc = check_aligned(who, "priority", priority, 4)) return rc;
+    if (const int rc = check_aligned(who, "next_xy", next_xy, 4)) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::CostToGoParams cp{};
+    if (const int rc = cost_to_go_cache(e, s, who, &cp)) return rc;
+    PGX_HIP(pgx::launch_cost_to_go_refresh(cp, s));
+    pgx::PibtParams p{cp};  // (the StateView base of cp; the planner's own fields follow)
+    p.action_dtype = action_dtype;
+    p.cell_bytes = cp.cell_bytes;
+    p.field = cp.field;
+    p.priority = priority;
+    p.actions = actions;
+    p.next_xy = next_xy;
+    PGX_HIP(pgx::launch_pibt_swap(p, s));
+    return PGX_OK;
+}
+
 // ---- multi-step planner (docs/SPEC.md S16) ----------------------------------------------------------------
 int pgx_pibt_plan(pgx_env* e, int32_t flags, int32_t horizon, const int32_t* priority, void* actions, int32_t action_dtype,
                   int32_t* path_xy, int32_t* arrival, int32_t* priority_out, void* stream) {

@@ -408,6 +408,9 @@ struct PibtParams : StateView {
     int32_t* next_xy;        // [B][A][2] unpadded, may be null
 };
 hipError_t launch_pibt(const PibtParams& p, hipStream_t stream);
+// the planner with the swap operation (pgx_pibt_swap.hip, docs/SPEC.md S23): the same arguments, `tgt` is read too
+enum { SWAP_MAX_WALK = 2048 };                // PGX_SWAP_MAX_WALK: steps of one corridor walk
+hipError_t launch_pibt_swap(const PibtParams& p, hipStream_t stream);
 
 // ---- multi-step planner (pgx_pibt_horizon.hip): the planner iterated over a horizon in one launch ----------------
 struct PibtPlanParams : PibtParams {   // `actions` is [horizon][B][A]; `next_xy` is not used

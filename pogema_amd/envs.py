@@ -235,14 +235,14 @@ class Pogema:
         return [[(int(j), int(d[0]), int(d[1])) for j, d in zip(index[i], offset[i]) if j >= 0]
                 for i in range(index.shape[0])]
 
-    def pibt_actions(self, priority=None):
+    def pibt_actions(self, priority=None, swap=False):
         """The cooperative planner's action for every agent (VecPogema.pibt_actions), as a list for step().  `priority`:
-        one integer per agent, None = all equal."""
+        one integer per agent, None = all equal.  `swap=True`: the planner with the swap operation (docs/SPEC.md S23)."""
         import torch
         vec = self._vec
         if priority is not None:
             priority = torch.as_tensor(np.asarray(priority, dtype=np.int64)[None], device=vec.device)
-        actions, _ = vec.pibt_actions(priority=priority)
+        actions, _ = vec.pibt_actions(priority=priority, swap=swap)
         return [int(a) for a in actions[0].cpu().numpy()]
 
     def pibt_plan(self, horizon, priority=None):

@@ -12,10 +12,16 @@ class PibtPolicy:
     `act(scores=...)` shields a learnt policy's action scores under the same priorities (VecPogema.shield_actions,
     docs/SPEC.md S15) and returns (actions, next_xy, overridden).
     `plan(horizon)` -> (actions, path_xy, arrival) for `env.rollout`: the same priorities grown inside the lookahead
-    (VecPogema.pibt_plan, docs/SPEC.md S16); no `update()` is needed between a plan and the next."""
+    (VecPogema.pibt_plan, docs/SPEC.md S16); no `update()` is needed between a plan and the next.
+    `PibtPolicy(env, swap=True)`: act() plans with the swap operation (VecPogema.pibt_actions(swap=True), docs/SPEC.md
+    S23), which clears the dead ends and corridors the plain rule livelocks in; act(scores=...) is unchanged, and plan()
+    raises: the multi-step planner has no swap rule yet."""
 
-    def __init__(self, env):
+    def __init__(self, env, swap=False):
+        if not isinstance(swap, bool):
+            raise TypeError(f"swap must be a bool, got {type(swap).__name__}")
         self.env = env
+        self.swap = swap
         self.priority = torch.zeros((env.batch, env.num_agents), dtype=torch.int32, device=env.device)
 
     def reset(self) -> None:
@@ -25,7 +31,7 @@ class PibtPolicy:
         if scores is None:
             if tie_break is not None:
                 raise ValueError("tie_break belongs to act(scores=...)")
-            return self.env.pibt_actions(priority=self.priority, dtype=dtype, out=out)
+            return self.env.pibt_actions(priority=self.priority, dtype=dtype, out=out, swap=self.swap)
         return self.env.shield_actions(scores, priority=self.priority, tie_break=tie_break, dtype=dtype, out=out)
 
     def plan(self, horizon, dtype=torch.int64, out=None):
@@ -35,6 +41,9 @@ class PibtPolicy:
         time limit, or every agent finished), zero that env's row of `self.priority` before planning again, as
         `update(rewards, episode_done)` does.  `out=(actions, path_xy, arrival, priority)` as VecPogema.pibt_plan takes
         it."""
+        if self.swap:
+            raise ValueError("plan() is not available on a PibtPolicy(env, swap=True): the multi-step planner "
+                             "(pibt_plan) has no swap rule yet; use act(), or a policy without swap")
         actions, path_xy, arrival, self.priority = self.env.pibt_plan(horizon, priority=self.priority, dtype=dtype,
                                                                      out=out)
         return actions, path_xy, arrival

@@ -182,7 +182,7 @@ class QueryMixin:
             raise ValueError(f"priority must have shape {shape} on {self.device}")
         return priority.to(torch.int32).contiguous()
 
-    def pibt_actions(self, priority=None, dtype=torch.int64, out=None):
+    def pibt_actions(self, priority=None, dtype=torch.int64, out=None, *, swap=False):
         """Cooperative one-step planner (PIBT, docs/SPEC.md S13), computed on the device from the current state -- the
         state the next step() reads, which this call leaves untouched.  Returns (actions [batch, agents] of `dtype`,
         next_xy int32 [batch, agents, 2]: the cell each agent is sent to, unpadded (row, col)).  Every active agent gets
@@ -194,15 +194,21 @@ class QueryMixin:
         `priority`: an integer tensor [batch, agents] on this device (converted to int32), None = all equal.
         Shares cost_to_go()'s cache: whichever is called first allocates it (not inside a graph capture); later calls are
         stream-ordered, need no host sync and can be captured.  `out=(actions, next_xy)`: caller-owned contiguous
-        tensors on this device (actions int8 / int32 / int64, next_xy int32)."""
+        tensors on this device (actions int8 / int32 / int64, next_xy int32).
+        `swap=True`: the planner with the swap operation (docs/SPEC.md S23, pgx_pibt_swap_actions) -- an agent that has
+        to pass another one in a corridor or a dead end tries its cells back to front and pulls the other agent into the
+        cell it leaves, which ends the livelocks of the plain rule there.  Same arguments, outputs, guarantees and cache
+        rules; a heuristic that loses a few instances the plain rule solves, hence opt-in."""
         B, A = self.batch, self.num_agents
+        if not isinstance(swap, (bool, np.bool_)):
+            raise TypeError(f"swap must be a bool, got {type(swap).__name__}")
         priority = self._priority(priority)
         actions, next_xy = _split(out, ("actions", "next_xy"))
         actions = query_output("out[actions]", actions, self._action_dtypes(dtype, actions), (B, A), self.device)
         next_xy = query_output("out[next_xy]", next_xy, torch.int32, (B, A, 2), self.device)
-        _lib.check(self._lib.pgx_pibt_actions(self._handle, 0, priority.data_ptr() if priority is not None else None,
-                                              actions.data_ptr(), self._ACTION_CODE[actions.dtype], next_xy.data_ptr(),
-                                              self._stream()))
+        call = self._lib.pgx_pibt_swap_actions if swap else self._lib.pgx_pibt_actions
+        _lib.check(call(self._handle, 0, priority.data_ptr() if priority is not None else None, actions.data_ptr(),
+                        self._ACTION_CODE[actions.dtype], next_xy.data_ptr(), self._stream()))
         return actions, next_xy
 
     def pibt_plan(self, horizon, priority=None, growing: bool = True, dtype=torch.int64, out=None):
