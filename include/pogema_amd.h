@@ -627,6 +627,46 @@ int pgx_goal_directions(pgx_env* env, int32_t flags, void* out, int32_t format, 
 int pgx_goal_paths(pgx_env* env, int32_t flags, int32_t steps, int32_t format, void* planes, int8_t* subgoal,
                    int32_t* length, void* stream);
 
+/* Agent forecasts (docs/SPEC.md S24), the planes PRIMAL2-style policies add to their input: where the other agents an
+ * observer can see are going to be at t+1 .. t+K if each follows its own shortest path -- read from the current device
+ * state, the state the next pgx_step reads, which this call does not change.  With r = obs_radius, W = 2r + 1, K = steps
+ * and D_j agent j's distance field (pgx_cost_to_go's), the FORECAST of an agent at cell p0 is q(0) = p0, q(s+1) = q(s) +
+ * MOVES[a] for the lowest a of 1..4 (up, down, left, right) whose destination lies inside the map and has a defined
+ * distance strictly smaller than q(s)'s -- pgx_goal_paths' rule with no window ending it -- and q(s+1) = q(s) when there is
+ * no such move (on the target, or no defined distance at q(s)): it waits there for all later s.  Other agents are not
+ * obstacles.  The trip count is exactly K whatever a field holds.  An agent that is not active (bit 0 of is_active
+ * clear) has no forecast and its field is not read.
+ *   steps    K, 1..PGX_MAX_FORECAST_STEPS
+ *   format   of `planes`, checked even when `planes` is NULL:
+ *            PGX_FORECAST_F32   f32 [batch, agents, K, W, W]  plane s-1 of observer i is 1.0 at window cell (u, v) iff i
+ *                               is active and some active agent j != i that i sees NOW (|x_j - x_i| <= r and
+ *                               |y_j - y_i| <= r, pgx_visible_agents' rule, every such agent however many) has
+ *                               q_j(s) - p0_i = (u - r, v - r); else 0.0 (4-byte aligned).  The orientation of
+ *                               observation plane 0.  A forecast cell outside the window is not drawn (no clamp), two
+ *                               forecasts on one cell give 1, the ghost bit does not matter, the observer's own
+ *                               forecast is not in its planes.
+ *            PGX_FORECAST_U8    u8  [batch, agents, K, W, W]  1 / 0
+ *            PGX_FORECAST_ROWS  i32 [batch, agents, K, W]     bit v of word u = cell (u, v); bit 31 is never set (4-byte
+ *                               aligned)
+ *   flags    reserved, must be 0
+ *   planes   device buffer of `format`, or NULL: no plane is written at all.  A 16-byte aligned `planes` is written
+ *            with 16-byte stores, any other with one store per element.
+ *   cells    device i16 [batch, agents, K, 2], 2-byte aligned, never NULL (the plane pass reads it): cells[b, j, s-1] =
+ *            q_j(s) as (x, y) in pgx_get_state's coordinates; (-1, -1) for every s of an agent that is not active.
+ * Shares pgx_cost_to_go's distance-field cache exactly as pgx_goal_paths does: the call refreshes it (stale fields are
+ * rebuilt and counted by pgx_cost_to_go_builds), then walks every agent in one launch and, with `planes`, gathers in a
+ * second one; whichever entry point uses the cache first allocates it -- inside a graph capture that first call returns
+ * PGX_E_STATE, a failed allocation PGX_E_NOMEM / PGX_E_HIP naming the bytes.  Afterwards asynchronous on `stream`, no
+ * host sync, capturable in a HIP graph.  PGX_E_INVALID for a NULL `cells`, non-zero flags, an unknown format, steps
+ * outside 1..PGX_MAX_FORECAST_STEPS, a misaligned float32 or rows `planes` or an odd `cells` address (checked before the
+ * handle: no device needed); PGX_E_STATE before the first reset, like pgx_step. */
+#define PGX_FORECAST_F32 0
+#define PGX_FORECAST_U8 1
+#define PGX_FORECAST_ROWS 2
+#define PGX_MAX_FORECAST_STEPS 8
+int pgx_agent_forecasts(pgx_env* env, int32_t steps, int32_t format, int32_t flags, void* planes, int16_t* cells,
+                        void* stream);
+
 /* Policy input (docs/SPEC.md S18): the stack of binary window planes a learnt MAPF policy reads, written once, in the
  * order and the number format the network takes -- read from the current device state, the state the next pgx_step
  * reads, which this call does not change.  Plane c of every agent's window is the channel channels[c]:

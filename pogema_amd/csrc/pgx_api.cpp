@@ -1093,7 +1093,7 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
 
 // The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
 // first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_goal_directions,
-// pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE, pgx_policy_input with a direction channel, pgx_agent_tokens, pgx_goal_paths).  `who` names that entry point in the error messages.
+// pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE, pgx_policy_input with a direction channel, pgx_agent_tokens, pgx_goal_paths, pgx_agent_forecasts).  `who` names that entry point in the error messages.
 static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p) {
     const pgx_config& c = e->cfg;
     const pgx::CostToGoLayout l = pgx::cost_to_go_layout(c.batch, c.num_agents, c.height, c.width);
@@ -1360,6 +1360,34 @@ int pgx_goal_paths(pgx_env* e, int32_t flags, int32_t steps, int32_t format, voi
     p.subgoal = subgoal;
     p.length = length;
     PGX_HIP(pgx::launch_goal_paths(p, s));
+    return PGX_OK;
+}
+
+// ---- agent forecasts (docs/SPEC.md S24) ---------------------------------------------------------------------
+int pgx_agent_forecasts(pgx_env* e, int32_t steps, int32_t format, int32_t flags, void* planes, int16_t* cells, void* stream) {
+    static const char who[] = "pgx_agent_forecasts";
+    // the argument checks come first and need no device
+    if (!cells) return fail_msg(PGX_E_INVALID, "%s: cells is null", who);
+    if (const int rc = check_flags(who, flags, 0)) return rc;
+    static_assert(PGX_FORECAST_F32 == pgx::FORECAST_F32 && PGX_FORECAST_U8 == pgx::FORECAST_U8 &&
+                      PGX_FORECAST_ROWS == pgx::FORECAST_ROWS, "the kernels' format codes are the header's");
+    if (format != PGX_FORECAST_F32 && format != PGX_FORECAST_U8 && format != PGX_FORECAST_ROWS)
+        return fail_msg(PGX_E_INVALID, "%s: bad format %d", who, format);
+    if (steps < 1 || steps > PGX_MAX_FORECAST_STEPS)
+        return fail_msg(PGX_E_INVALID, "%s: steps %d is outside 1..%d", who, steps, PGX_MAX_FORECAST_STEPS);
+    if (format != PGX_FORECAST_U8)
+        if (const int rc = check_aligned(who, format == PGX_FORECAST_F32 ? "a float32 planes" : "a rows planes", planes, 4)) return rc;
+    if (const int rc = check_aligned(who, "cells", cells, 2)) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::ForecastParams p{};
+    if (const int rc = cost_to_go_cache(e, s, who, &p)) return rc;  // (fills the CostToGoParams base of p)
+    p.format = format;
+    p.steps = steps;
+    p.planes = planes;
+    p.cells = cells;
+    PGX_HIP(pgx::launch_agent_forecasts(p, s));
     return PGX_OK;
 }
 

@@ -347,6 +347,18 @@ struct GoalPathParams : CostToGoParams {   // `out` is not used
 // the refresh of the cost-to-go cache `p` describes, then the paths of every agent in one launch
 hipError_t launch_goal_paths(const GoalPathParams& p, hipStream_t stream);
 
+// ---- agent forecasts (pgx_agent_forecasts.hip, docs/SPEC.md S24) ---------------------------------------------
+enum { FORECAST_F32 = 0, FORECAST_U8 = 1, FORECAST_ROWS = 2 };  // PGX_FORECAST_* (include/pogema_amd.h)
+struct ForecastParams : CostToGoParams {   // `out` is not used
+    int32_t format;          // FORECAST_*: the elements of `planes`
+    int32_t steps;           // K, 1..PGX_MAX_FORECAST_STEPS: the walk's trip count, whatever a field holds
+    void* planes;            // [B][A][K][2r+1][2r+1] float32 or u8, or [B][A][K][2r+1] i32 row masks; may be null
+    int16_t* cells;          // [B][A][K][2] unpadded (x, y) after 1..K steps, -1 for an inactive agent; never null
+};
+// the refresh of the cost-to-go cache `p` describes, then every agent's walk into `cells` and, with `planes`, the
+// gather of the visible agents' cells into every observer's planes: two launches
+hipError_t launch_agent_forecasts(const ForecastParams& p, hipStream_t stream);
+
 // ---- agent tokens (pgx_agent_tokens.hip): one row of token ids per agent (docs/SPEC.md S21) -------------------------
 struct TokenParams : CostToGoParams {   // `out` is not used
     int32_t slots;           // S, 1..PGX_MAX_TOKEN_SLOTS: the agent itself and S - 1 neighbours

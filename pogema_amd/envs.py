@@ -198,6 +198,12 @@ class Pogema:
         planes, subgoal, length = (t[0].cpu().numpy() for t in self._vec.goal_paths(steps=steps, format="uint8"))
         return [(planes[i], (int(subgoal[i][0]), int(subgoal[i][1])), int(length[i])) for i in range(planes.shape[0])]
 
+    def agent_forecasts(self, steps=3):
+        """Where the agents each agent sees will be after 1..`steps` steps (VecPogema.agent_forecasts) as a list of
+        (planes uint8 (K, W, W), cells) tuples: the agent's forecast planes and its own forecast cells as K (x, y) tuples."""
+        planes, cells = (t[0].cpu().numpy() for t in self._vec.agent_forecasts(steps=steps, format="uint8"))
+        return [(planes[i], [(int(x), int(y)) for x, y in cells[i]]) for i in range(planes.shape[0])]
+
     def policy_input(self, channels=_DEFAULT_POLICY_CHANNELS):
         """The network's input planes of every agent (VecPogema.policy_input) as a list of uint8 (C, W, W) numpy
         arrays, plane c the channel channels[c]."""

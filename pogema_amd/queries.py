@@ -1,6 +1,6 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
 cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes, path-to-goal planes,
-move outcomes, the policy input, the global state and the agent tokens.  Each is one C-ABI
+agent forecasts, move outcomes, the policy input, the global state and the agent tokens.  Each is one C-ABI
 call into caller-owned or fresh output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
 from __future__ import annotations
@@ -91,6 +91,23 @@ def check_global_ids(codes, dtype, num_agents):
                          f"has {num_agents}: use torch.float16 or torch.float32")
 
 
+def parse_forecast_steps(steps=3):
+    """The `steps` of agent_forecasts() as an int: an integer (a bool is none) in 1.._lib.MAX_FORECAST_STEPS, anything
+    else is a ValueError that names the range.  Needs no engine and no GPU."""
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= _lib.MAX_FORECAST_STEPS:
+        raise ValueError(f"steps must be an integer in 1..{_lib.MAX_FORECAST_STEPS}, got {steps!r}")
+    return int(steps)
+
+
+def parse_forecast_format(format="float32"):
+    """The `format` of agent_forecasts() as (PGX_FORECAST_* code, the planes' dtype, True when a plane is one int32 word
+    per row); a name outside _lib.FORECAST_FORMATS is a ValueError that lists the table.  Needs no engine and no GPU."""
+    if not isinstance(format, str) or format not in _lib.FORECAST_FORMATS:
+        raise ValueError(f"format must be one of {sorted(_lib.FORECAST_FORMATS)}, got {format!r}")
+    dtype = {"float32": torch.float32, "uint8": torch.uint8, "rows": torch.int32}[format]
+    return _lib.FORECAST_FORMATS[format], dtype, format == "rows"
+
+
 class QueryMixin:
     """The queries of a VecPogema.  Expects of the class it is mixed into: `_handle`, `_lib`, `device`, `batch`,
     `num_agents`, `window`, `height`, `width`, `_ACTION_CODE`, `_prepare_actions()`, `_stream()`."""
@@ -138,7 +155,7 @@ class QueryMixin:
 
     @property
     def cost_to_go_builds(self) -> int:
-        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), goal_directions(), goal_paths(), agent_tokens() and
+        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), goal_directions(), goal_paths(), agent_forecasts(), agent_tokens() and
         shield_actions(tie_break="distance") have built since this env was created (synchronises the stream)."""
         n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
         if n < 0:
@@ -357,6 +374,45 @@ class QueryMixin:
                                             plane_out.data_ptr() if plane_out is not None else None, subgoal.data_ptr(),
                                             length.data_ptr(), self._stream()))
         return plane_out, subgoal, length
+
+    def agent_forecasts(self, steps: int = 3, format: str = "float32", planes: bool = True, out=None):
+        """Agent forecasts (docs/SPEC.md S24), the planes PRIMAL2-style policies add to their input: where the other
+        agents an observer can see are going to be at t+1 .. t+K (K = `steps`) if each follows its own shortest path --
+        computed on the device from the current state, the state the next step() reads, which this call leaves
+        untouched.  An agent's forecast descends its distance field from its own cell for K steps: at every cell the
+        lowest of the moves 1..4 (up, down, left, right) that leads to a cell strictly closer to the target -- goal_paths()'
+        rule with no window ending it, so its first cell is the one expert_actions() moves to -- and it waits where nothing
+        is closer (on the target, or without a path).  Other agents are not obstacles.  Returns
+            (planes [batch, agents, K, W, W] (W = 2 * obs_radius + 1, the orientation of observation plane 0): plane s-1
+                 of an active observer is 1 on the window cells that hold the step-s forecast cell of another active
+                 agent it sees now (visible_agents()' rule; every such agent, however many).  A forecast cell outside
+                 the window is not drawn, the observer's own forecast is not in its planes, an inactive observer gets
+                 zeros.  None with `planes=False`;
+             cells int16 [batch, agents, K, 2]: every agent's own forecast cells (x, y) in get_state()'s coordinates;
+                 (-1, -1) for an inactive agent).
+        `steps`: an integer in 1..MAX_FORECAST_STEPS (8).
+        `format`: "float32" -> float32 [batch, agents, K, W, W] of 0.0 / 1.0;
+                  "uint8"   -> uint8 [batch, agents, K, W, W] of 0 / 1;
+                  "rows"    -> int32 [batch, agents, K, W], bit v of word u = cell (u, v).
+        `planes=False` writes no planes at all: the cells alone, in one launch instead of two.
+        Shares cost_to_go()'s cache under goal_paths()' rules: stale fields are rebuilt first, whichever call is first
+        allocates the cache (not inside a graph capture); later calls are stream-ordered, need no host sync and can be
+        captured.  `out=(planes, cells)`, with `planes=False` `out=(cells,)`: caller-owned contiguous tensors of those
+        dtypes and shapes on this device; a 16-byte aligned `planes` is written fastest."""
+        B, A, W = self.batch, self.num_agents, self.window
+        code, dtype, rows = parse_forecast_format(format)
+        K = parse_forecast_steps(steps)
+        if planes:
+            plane_out, cells = _split(out, ("planes", "cells"))
+            plane_out = query_output("out[planes]", plane_out, dtype, (B, A, K, W) if rows else (B, A, K, W, W), self.device)
+        else:
+            plane_out = None
+            cells, = _split(out, ("cells",))
+        cells = query_output("out[cells]", cells, torch.int16, (B, A, K, 2), self.device)
+        _lib.check(self._lib.pgx_agent_forecasts(self._handle, K, code, 0,
+                                                 plane_out.data_ptr() if plane_out is not None else None, cells.data_ptr(),
+                                                 self._stream()))
+        return plane_out, cells
 
     def move_outcomes(self, actions, out=None):
         """Move outcomes (docs/SPEC.md S17): what the move phase of step(actions) would do to every agent and why a move
