@@ -667,6 +667,32 @@ int pgx_goal_paths(pgx_env* env, int32_t flags, int32_t steps, int32_t format, v
 int pgx_agent_forecasts(pgx_env* env, int32_t steps, int32_t format, int32_t flags, void* planes, int16_t* cells,
                         void* stream);
 
+/* Blocking counts (docs/SPEC.md S25), the blocking penalty of PRIMAL / PRIMAL2 / SCRIMP style rewards: which agents
+ * stand in the way of others -- read from the current device state, the state the next pgx_step reads, which this call
+ * does not change.  Agents are never obstacles for each other's paths; only the one blocker under test is.  For an
+ * ordered pair (i, j), i != j, of one env with c = cell of i, s = cell of j, t = target of j and d0 = D_j[s] (D_j agent j's
+ * distance field, pgx_cost_to_go's), the pair is ELIGIBLE iff both are active (bit 0 of is_active), j is visible to i by
+ * pgx_visible_agents' rule (|x_j - x_i| <= r and |y_j - y_i| <= r, every such agent however many) and, with
+ * PGX_BLOCKING_ON_TARGET, i stands on its own target.  i BLOCKS j iff the pair is eligible, d0 is defined, s != c and no
+ * path from s to t of at most d0 + inflation - 1 steps exists on the map with cell c made an obstacle: a detour of at
+ * least `inflation` steps, a cut-off agent and c == t alike.
+ *   inflation   1..PGX_MAX_BLOCKING_INFLATION (PRIMAL uses 10; 1: "c lies on every shortest path of j")
+ *   flags       0 or PGX_BLOCKING_ON_TARGET
+ *   count       device i32 [batch, agents], 4-byte aligned, or NULL: count[b, i] = the number of j that i blocks
+ *   blocked_by  device i32 [batch, agents], 4-byte aligned, or NULL: blocked_by[b, j] = the number of i that block j
+ * Agents that are not active get 0 in both; per env the two outputs have the same sum.  A pair with D_j[c] undefined or
+ * D_j[c] + |c - s|_1 > d0 is not blocked and is dismissed without a search (c is on no shortest path of j); every other
+ * eligible pair takes one breadth-first search of at most d0 + inflation - 1 levels that ends as soon as t is reached.
+ * Shares pgx_cost_to_go's distance-field cache exactly as pgx_goal_paths does: the call refreshes it (stale fields are
+ * rebuilt and counted by pgx_cost_to_go_builds) and then counts; whichever entry point uses the cache first allocates
+ * it -- inside a graph capture that first call returns PGX_E_STATE, a failed allocation PGX_E_NOMEM / PGX_E_HIP naming the
+ * bytes.  Afterwards asynchronous on `stream`, no host sync, capturable in a HIP graph.  PGX_E_INVALID when both outputs
+ * are NULL, for an inflation outside 1..PGX_MAX_BLOCKING_INFLATION, an unknown flag bit or a misaligned output (checked
+ * before the handle: no device needed); PGX_E_STATE before the first reset, like pgx_step. */
+#define PGX_BLOCKING_ON_TARGET 1
+#define PGX_MAX_BLOCKING_INFLATION 64
+int pgx_blocking(pgx_env* env, int32_t inflation, int32_t flags, int32_t* count, int32_t* blocked_by, void* stream);
+
 /* Policy input (docs/SPEC.md S18): the stack of binary window planes a learnt MAPF policy reads, written once, in the
  * order and the number format the network takes -- read from the current device state, the state the next pgx_step
  * reads, which this call does not change.  Plane c of every agent's window is the channel channels[c]:

@@ -60,6 +60,9 @@ PATHS_FORMATS = {"float32": 0, "uint8": 1, "rows": 2}  # PGX_PATHS_*: formats of
 MAX_PATH_STEPS = 960  # PGX_MAX_PATH_STEPS: the largest cap of pgx_goal_paths, 31 * 31 - 1
 FORECAST_FORMATS = {"float32": 0, "uint8": 1, "rows": 2}  # PGX_FORECAST_*: formats of pgx_agent_forecasts' planes (docs/SPEC.md S24)
 MAX_FORECAST_STEPS = 8  # PGX_MAX_FORECAST_STEPS: the most steps of pgx_agent_forecasts
+BLOCKING_BLOCKERS = {"all": 0, "on_target": 1}  # flags of pgx_blocking (PGX_BLOCKING_ON_TARGET; docs/SPEC.md S25)
+BLOCKING_ON_TARGET = 1  # PGX_BLOCKING_ON_TARGET
+MAX_BLOCKING_INFLATION = 64  # PGX_MAX_BLOCKING_INFLATION: the largest inflation of pgx_blocking
 SHIELD_TIE_BREAKS = {None: 0, "distance": 1}  # flags of pgx_shield_actions (PGX_SHIELD_TIE_DISTANCE)
 MAX_PLAN_HORIZON = 256  # PGX_MAX_PLAN_HORIZON: steps of one pgx_pibt_plan
 PLAN_FIXED_PRIORITY = 1  # PGX_PLAN_FIXED_PRIORITY: flag of pgx_pibt_plan
@@ -111,7 +114,7 @@ EXPORTED_SYMBOLS = (
     "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan", "pgx_move_outcomes",
     "pgx_policy_input", "pgx_copy_envs", "pgx_global_state", "pgx_global_state_check",
     "pgx_agent_tokens", "pgx_agent_tokens_length", "pgx_goal_paths", "pgx_pibt_swap_actions",
-    "pgx_agent_forecasts",
+    "pgx_agent_forecasts", "pgx_blocking",
 )
 
 
@@ -255,6 +258,8 @@ def load() -> C.CDLL:
     lib.pgx_goal_paths.restype = C.c_int
     lib.pgx_agent_forecasts.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     lib.pgx_agent_forecasts.restype = C.c_int
+    lib.pgx_blocking.argtypes = [vp, i32, i32, vp, vp, vp]
+    lib.pgx_blocking.restype = C.c_int
     lib.pgx_copy_envs.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.pgx_copy_envs.restype = C.c_int
     lib.pgx_set_map_pool.argtypes = [vp, vp, i32, vp, vp]

@@ -1093,7 +1093,7 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
 
 // The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
 // first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_goal_directions,
-// pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE, pgx_policy_input with a direction channel, pgx_agent_tokens, pgx_goal_paths, pgx_agent_forecasts).  `who` names that entry point in the error messages.
+// pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE, pgx_policy_input with a direction channel, pgx_agent_tokens, pgx_goal_paths, pgx_agent_forecasts, pgx_blocking).  `who` names that entry point in the error messages.
 static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p) {
     const pgx_config& c = e->cfg;
     const pgx::CostToGoLayout l = pgx::cost_to_go_layout(c.batch, c.num_agents, c.height, c.width);
@@ -1388,6 +1388,29 @@ int pgx_agent_forecasts(pgx_env* e, int32_t steps, int32_t format, int32_t flags
     p.planes = planes;
     p.cells = cells;
     PGX_HIP(pgx::launch_agent_forecasts(p, s));
+    return PGX_OK;
+}
+
+// ---- blocking counts (docs/SPEC.md S25) ---------------------------------------------------------------------
+int pgx_blocking(pgx_env* e, int32_t inflation, int32_t flags, int32_t* count, int32_t* blocked_by, void* stream) {
+    static const char who[] = "pgx_blocking";
+    // the argument checks come first and need no device
+    if (!count && !blocked_by) return fail_msg(PGX_E_INVALID, "%s: count and blocked_by are both null", who);
+    if (const int rc = check_flags(who, flags, PGX_BLOCKING_ON_TARGET)) return rc;
+    if (inflation < 1 || inflation > PGX_MAX_BLOCKING_INFLATION)
+        return fail_msg(PGX_E_INVALID, "%s: inflation %d is outside 1..%d", who, inflation, PGX_MAX_BLOCKING_INFLATION);
+    if (const int rc = check_aligned(who, "count", count, 4)) return rc;
+    if (const int rc = check_aligned(who, "blocked_by", blocked_by, 4)) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    pgx::BlockingParams p{};
+    if (const int rc = cost_to_go_cache(e, s, who, &p)) return rc;  // (fills the CostToGoParams base of p)
+    p.inflation = inflation;
+    p.on_target = (flags & PGX_BLOCKING_ON_TARGET) ? 1 : 0;
+    p.count = count;
+    p.blocked_by = blocked_by;
+    PGX_HIP(pgx::launch_blocking(p, s));
     return PGX_OK;
 }
 

@@ -359,6 +359,17 @@ struct ForecastParams : CostToGoParams {   // `out` is not used
 // gather of the visible agents' cells into every observer's planes: two launches
 hipError_t launch_agent_forecasts(const ForecastParams& p, hipStream_t stream);
 
+// ---- blocking counts (pgx_blocking.hip, docs/SPEC.md S25) -----------------------------------------------------
+struct BlockingParams : CostToGoParams {   // `out` is not used
+    int32_t inflation;       // 1..PGX_MAX_BLOCKING_INFLATION: a search runs at most d0 + inflation - 1 levels
+    int32_t on_target;       // only agents standing on their own target block (PGX_BLOCKING_ON_TARGET)
+    int32_t* count;          // [B][A] agents this one blocks; may be null
+    int32_t* blocked_by;     // [B][A] agents that block this one; may be null
+};
+// the refresh of the cost-to-go cache `p` describes, then the counts (small layout: one launch; large: a zeroing launch
+// of `count` and the search launch)
+hipError_t launch_blocking(const BlockingParams& p, hipStream_t stream);
+
 // ---- agent tokens (pgx_agent_tokens.hip): one row of token ids per agent (docs/SPEC.md S21) -------------------------
 struct TokenParams : CostToGoParams {   // `out` is not used
     int32_t slots;           // S, 1..PGX_MAX_TOKEN_SLOTS: the agent itself and S - 1 neighbours

@@ -204,6 +204,12 @@ class Pogema:
         planes, cells = (t[0].cpu().numpy() for t in self._vec.agent_forecasts(steps=steps, format="uint8"))
         return [(planes[i], [(int(x), int(y)) for x, y in cells[i]]) for i in range(planes.shape[0])]
 
+    def blocking(self, inflation=10, blockers="all"):
+        """Which agents stand in the way of others (VecPogema.blocking) as two lists of ints: count[i], the number of
+        agents that agent i blocks, and blocked_by[j], the number of agents that block agent j."""
+        count, blocked_by = (t[0].cpu().numpy() for t in self._vec.blocking(inflation=inflation, blockers=blockers))
+        return [int(c) for c in count], [int(c) for c in blocked_by]
+
     def policy_input(self, channels=_DEFAULT_POLICY_CHANNELS):
         """The network's input planes of every agent (VecPogema.policy_input) as a list of uint8 (C, W, W) numpy
         arrays, plane c the channel channels[c]."""

@@ -1,6 +1,6 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
 cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes, path-to-goal planes,
-agent forecasts, move outcomes, the policy input, the global state and the agent tokens.  Each is one C-ABI
+agent forecasts, blocking counts, move outcomes, the policy input, the global state and the agent tokens.  Each is one C-ABI
 call into caller-owned or fresh output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
 from __future__ import annotations
@@ -108,6 +108,25 @@ def parse_forecast_format(format="float32"):
     return _lib.FORECAST_FORMATS[format], dtype, format == "rows"
 
 
+def parse_blocking_inflation(inflation=10):
+    """The `inflation` of blocking() as an int: an integer (a bool is none) in 1.._lib.MAX_BLOCKING_INFLATION.  Anything
+    that is no integer is a TypeError, an integer outside the range a ValueError that names it.  Needs no engine and no
+    GPU."""
+    if isinstance(inflation, bool) or not isinstance(inflation, (int, np.integer)):
+        raise TypeError(f"inflation must be an integer in 1..{_lib.MAX_BLOCKING_INFLATION}, got {type(inflation).__name__}")
+    if not 1 <= inflation <= _lib.MAX_BLOCKING_INFLATION:
+        raise ValueError(f"inflation must be an integer in 1..{_lib.MAX_BLOCKING_INFLATION}, got {inflation!r}")
+    return int(inflation)
+
+
+def parse_blockers(blockers="all"):
+    """The `blockers` of blocking() as pgx_blocking's flags; a name outside _lib.BLOCKING_BLOCKERS is a ValueError that
+    lists the vocabulary.  Needs no engine and no GPU."""
+    if not isinstance(blockers, str) or blockers not in _lib.BLOCKING_BLOCKERS:
+        raise ValueError(f"blockers must be one of {sorted(_lib.BLOCKING_BLOCKERS)}, got {blockers!r}")
+    return _lib.BLOCKING_BLOCKERS[blockers]
+
+
 class QueryMixin:
     """The queries of a VecPogema.  Expects of the class it is mixed into: `_handle`, `_lib`, `device`, `batch`,
     `num_agents`, `window`, `height`, `width`, `_ACTION_CODE`, `_prepare_actions()`, `_stream()`."""
@@ -155,7 +174,7 @@ class QueryMixin:
 
     @property
     def cost_to_go_builds(self) -> int:
-        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), goal_directions(), goal_paths(), agent_forecasts(), agent_tokens() and
+        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), goal_directions(), goal_paths(), agent_forecasts(), blocking(), agent_tokens() and
         shield_actions(tie_break="distance") have built since this env was created (synchronises the stream)."""
         n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
         if n < 0:
@@ -413,6 +432,34 @@ class QueryMixin:
                                                  plane_out.data_ptr() if plane_out is not None else None, cells.data_ptr(),
                                                  self._stream()))
         return plane_out, cells
+
+    def blocking(self, inflation: int = 10, blockers: str = "all", out=None):
+        """Blocking counts (docs/SPEC.md S25), the blocking penalty of PRIMAL / PRIMAL2 / SCRIMP style rewards: which
+        agents stand in the way of others -- computed on the device from the current state, the state the next step()
+        reads, which this call leaves untouched.  Agent i blocks agent j of the same env iff both are active, i sees j
+        (visible_agents()' rule; every such agent, however many), j has a path to its target at all, they stand on
+        different cells and, on the map with i's cell made an obstacle, j has no path to its target of fewer than
+        `inflation` steps more than its shortest one: a detour of at least `inflation` steps, a cut-off agent and an
+        agent sitting on j's target alike.  Other agents are never obstacles for these paths.  Returns
+            (count int32 [batch, agents]: the number of agents that agent i blocks;
+             blocked_by int32 [batch, agents]: the number of agents that block agent j).
+        Inactive agents get 0 in both; per env the two have the same sum.
+        `inflation`: an integer in 1..MAX_BLOCKING_INFLATION (64); PRIMAL uses 10; 1 asks whether i stands on every
+        shortest path of j.  `blockers`: "all", or "on_target": only agents standing on their own target block.
+        A pair whose blocker lies on no shortest path of j is dismissed from the cached distance fields alone; the
+        others take one bounded search each.  Shares cost_to_go()'s cache under goal_paths()' rules: stale fields are
+        rebuilt first, whichever call is first allocates the cache (not inside a graph capture); later calls are
+        stream-ordered, need no host sync and can be captured.  `out=(count, blocked_by)`: caller-owned contiguous int32
+        tensors of that shape on this device."""
+        B, A = self.batch, self.num_agents
+        inflation = parse_blocking_inflation(inflation)
+        flags = parse_blockers(blockers)
+        count, blocked_by = _split(out, ("count", "blocked_by"))
+        count = query_output("out[count]", count, torch.int32, (B, A), self.device)
+        blocked_by = query_output("out[blocked_by]", blocked_by, torch.int32, (B, A), self.device)
+        _lib.check(self._lib.pgx_blocking(self._handle, inflation, flags, count.data_ptr(), blocked_by.data_ptr(),
+                                          self._stream()))
+        return count, blocked_by
 
     def move_outcomes(self, actions, out=None):
         """Move outcomes (docs/SPEC.md S17): what the move phase of step(actions) would do to every agent and why a move
