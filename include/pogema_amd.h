@@ -693,6 +693,48 @@ int pgx_agent_forecasts(pgx_env* env, int32_t steps, int32_t format, int32_t fla
 #define PGX_MAX_BLOCKING_INFLATION 64
 int pgx_blocking(pgx_env* env, int32_t inflation, int32_t flags, int32_t* count, int32_t* blocked_by, void* stream);
 
+/* Path conflicts (docs/SPEC.md S26): where K-step paths run into each other, per agent -- the conflict count and first
+ * conflict of conflict-based priorities, the "who is in my way" of selective communication, a K-step collision signal,
+ * and the validator of a plan.  Reads the current device state, the state the next pgx_step reads, and the caller's
+ * paths; changes neither.  With K = steps, pos_0[i] the agent's current cell, pos_h[i] = the path's cell h (h = 1..K) and
+ * tgt[i] its current target, agent i TAKES PART at h (h = 0..K) iff bit 0 of is_active is set, pos_h[i] lies inside the
+ * H x W map and, when agents vanish, no h' < h has pos_h'[i] == tgt[i].  Cells are keys, not moves: consecutive cells need
+ * not be adjacent, any int value is a cell outside the map.  For h >= 1 and agents i != j of one env:
+ *   PGX_CONFLICT_VERTEX  both take part at h and pos_h[i] == pos_h[j]
+ *   PGX_CONFLICT_EDGE    both take part at h and h-1, pos_h[i] == pos_h-1[j], pos_h[j] == pos_h-1[i], pos_h[i] != pos_h-1[i]
+ *   PGX_CONFLICT_FOLLOW  (on the follower i only) both take part at h and h-1, pos_h[i] == pos_h-1[j],
+ *                        pos_h[i] != pos_h-1[i], pos_h[j] != pos_h-1[j], and not an edge conflict
+ * The kinds exclude each other for one (h, i, j).  An INCIDENCE of i is a pair (h, j) in a kind named in `flags`.
+ *   paths       device buffer, never NULL, of `layout`:
+ *               PGX_CONFLICT_PATHS_PLAN   i32 [K, batch, agents, 2], 4-byte aligned: pgx_pibt_plan's path_xy
+ *               PGX_CONFLICT_PATHS_CELLS  i16 [batch, agents, K, 2], 2-byte aligned: pgx_agent_forecasts' cells
+ *               unpadded (x, y) in pgx_get_state's coordinates
+ *   steps       K, 1..PGX_MAX_CONFLICT_STEPS
+ *   flags       at least one of PGX_CONFLICT_VERTEX / _EDGE / _FOLLOW: the kinds that exist for this call; and at most
+ *               one of PGX_CONFLICT_STAY (an agent on its target keeps taking part) and PGX_CONFLICT_VANISH (it does not,
+ *               from the step after the first one on its target); with neither, agents vanish iff on_target is
+ *               PGX_ON_TARGET_FINISH -- pgx_pibt_plan's rule, so a plan is judged the way it was made
+ *   first_step  device i32 [batch, agents]: the smallest h with an incidence, -1 if none
+ *   partner     device i32 [batch, agents]: the lowest j over the incidences at first_step, -1 if none
+ *   kind        device u8  [batch, agents]: the OR of the kind bits over the incidences at first_step, 0 if none
+ *   count       device i32 [batch, agents]: the number of incidences over all h
+ * Each output may be NULL, not all four; the int32 ones are 4-byte aligned.  An agent that is not active gets -1, -1, 0,
+ * 0.  The results are a minimum, an OR and a sum over sets: deterministic.  One launch that reads no distance field and
+ * allocates nothing: asynchronous on `stream`, no host sync, capturable in a HIP graph from the first call.
+ * PGX_E_INVALID for a NULL `paths`, four NULL outputs, steps outside 1..PGX_MAX_CONFLICT_STEPS, an unknown layout, an
+ * unknown flag bit, no kind bit, both arrival flags, a misaligned `paths` or int32 output (checked before the handle: no
+ * device needed); PGX_E_STATE before the first reset, like pgx_step. */
+#define PGX_CONFLICT_PATHS_PLAN 0
+#define PGX_CONFLICT_PATHS_CELLS 1
+#define PGX_CONFLICT_VERTEX 1
+#define PGX_CONFLICT_EDGE 2
+#define PGX_CONFLICT_FOLLOW 4
+#define PGX_CONFLICT_STAY 8
+#define PGX_CONFLICT_VANISH 16
+#define PGX_MAX_CONFLICT_STEPS 256
+int pgx_path_conflicts(pgx_env* env, const void* paths, int32_t layout, int32_t steps, int32_t flags,
+                       int32_t* first_step, int32_t* partner, uint8_t* kind, int32_t* count, void* stream);
+
 /* Policy input (docs/SPEC.md S18): the stack of binary window planes a learnt MAPF policy reads, written once, in the
  * order and the number format the network takes -- read from the current device state, the state the next pgx_step
  * reads, which this call does not change.  Plane c of every agent's window is the channel channels[c]:

@@ -8,9 +8,10 @@ __version__ = "0.1.0"
 from .semantics import Semantics
 from ._lib import OUTCOMES, NUM_OUTCOMES  # the codes of move_outcomes(), index = code
 from ._lib import TOKENS  # the vocabulary of agent_tokens() (docs/SPEC.md S21)
+from ._lib import CONFLICT_KINDS  # the kind bits of path_conflicts(), name -> bit (docs/SPEC.md S26)
 from .tokens import token_length
 
-__all__ = ["GridConfig", "Semantics", "OUTCOMES", "NUM_OUTCOMES", "TOKENS", "token_length", "TokenHistory", "release_cached_buffers", "VecPogema", "PipelinedVecPogema", "PibtPolicy", "Pogema", "pogema_v0", "Easy8x8", "Normal8x8", "Hard8x8", "Easy16x16",
+__all__ = ["GridConfig", "Semantics", "OUTCOMES", "NUM_OUTCOMES", "CONFLICT_KINDS", "TOKENS", "token_length", "TokenHistory", "release_cached_buffers", "VecPogema", "PipelinedVecPogema", "PibtPolicy", "Pogema", "pogema_v0", "Easy8x8", "Normal8x8", "Hard8x8", "Easy16x16",
            "Hard16x16", "Easy32x32", "Hard32x32", "Easy64x64", "Hard64x64"]
 
 

@@ -63,6 +63,11 @@ MAX_FORECAST_STEPS = 8  # PGX_MAX_FORECAST_STEPS: the most steps of pgx_agent_fo
 BLOCKING_BLOCKERS = {"all": 0, "on_target": 1}  # flags of pgx_blocking (PGX_BLOCKING_ON_TARGET; docs/SPEC.md S25)
 BLOCKING_ON_TARGET = 1  # PGX_BLOCKING_ON_TARGET
 MAX_BLOCKING_INFLATION = 64  # PGX_MAX_BLOCKING_INFLATION: the largest inflation of pgx_blocking
+# PGX_CONFLICT_VERTEX / _EDGE / _FOLLOW: the kind bits of pgx_path_conflicts, name -> bit (docs/SPEC.md S26)
+CONFLICT_KINDS = {"vertex": 1, "edge": 2, "follow": 4}
+CONFLICT_ARRIVED = {None: 0, "stay": 8, "vanish": 16}  # PGX_CONFLICT_STAY / _VANISH; None: the engine's on_target decides
+CONFLICT_PATHS_PLAN, CONFLICT_PATHS_CELLS = 0, 1  # PGX_CONFLICT_PATHS_*: int32 [K, B, A, 2] / int16 [B, A, K, 2]
+MAX_CONFLICT_STEPS = 256  # PGX_MAX_CONFLICT_STEPS: steps of one pgx_path_conflicts, = MAX_PLAN_HORIZON
 SHIELD_TIE_BREAKS = {None: 0, "distance": 1}  # flags of pgx_shield_actions (PGX_SHIELD_TIE_DISTANCE)
 MAX_PLAN_HORIZON = 256  # PGX_MAX_PLAN_HORIZON: steps of one pgx_pibt_plan
 PLAN_FIXED_PRIORITY = 1  # PGX_PLAN_FIXED_PRIORITY: flag of pgx_pibt_plan
@@ -114,7 +119,7 @@ EXPORTED_SYMBOLS = (
     "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan", "pgx_move_outcomes",
     "pgx_policy_input", "pgx_copy_envs", "pgx_global_state", "pgx_global_state_check",
     "pgx_agent_tokens", "pgx_agent_tokens_length", "pgx_goal_paths", "pgx_pibt_swap_actions",
-    "pgx_agent_forecasts", "pgx_blocking",
+    "pgx_agent_forecasts", "pgx_blocking", "pgx_path_conflicts",
 )
 
 
@@ -260,6 +265,8 @@ def load() -> C.CDLL:
     lib.pgx_agent_forecasts.restype = C.c_int
     lib.pgx_blocking.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.pgx_blocking.restype = C.c_int
+    lib.pgx_path_conflicts.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.pgx_path_conflicts.restype = C.c_int
     lib.pgx_copy_envs.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.pgx_copy_envs.restype = C.c_int
     lib.pgx_set_map_pool.argtypes = [vp, vp, i32, vp, vp]

@@ -1414,6 +1414,47 @@ int pgx_blocking(pgx_env* e, int32_t inflation, int32_t flags, int32_t* count, i
     return PGX_OK;
 }
 
+// ---- path conflicts (docs/SPEC.md S26) ------------------------------------------------------------------------
+int pgx_path_conflicts(pgx_env* e, const void* paths, int32_t layout, int32_t steps, int32_t flags, int32_t* first_step,
+                       int32_t* partner, uint8_t* kind, int32_t* count, void* stream) {
+    static const char who[] = "pgx_path_conflicts";
+    // the argument checks come first and need no device
+    static_assert(PGX_CONFLICT_PATHS_PLAN == pgx::CONFLICT_PATHS_PLAN && PGX_CONFLICT_PATHS_CELLS == pgx::CONFLICT_PATHS_CELLS &&
+                      PGX_CONFLICT_VERTEX == pgx::CONFLICT_VERTEX && PGX_CONFLICT_EDGE == pgx::CONFLICT_EDGE &&
+                      PGX_CONFLICT_FOLLOW == pgx::CONFLICT_FOLLOW, "the kernel's layout and kind codes are the header's");
+    static_assert(PGX_MAX_CONFLICT_STEPS == PGX_MAX_PLAN_HORIZON, "a whole plan can be checked");
+    constexpr int32_t kinds = PGX_CONFLICT_VERTEX | PGX_CONFLICT_EDGE | PGX_CONFLICT_FOLLOW;
+    if (!paths) return fail_msg(PGX_E_INVALID, "%s: paths is null", who);
+    if (!first_step && !partner && !kind && !count) return fail_msg(PGX_E_INVALID, "%s: every output is null", who);
+    if (steps < 1 || steps > PGX_MAX_CONFLICT_STEPS)
+        return fail_msg(PGX_E_INVALID, "%s: steps %d is outside 1..%d", who, steps, PGX_MAX_CONFLICT_STEPS);
+    if (layout != PGX_CONFLICT_PATHS_PLAN && layout != PGX_CONFLICT_PATHS_CELLS)
+        return fail_msg(PGX_E_INVALID, "%s: bad layout %d", who, layout);
+    if (const int rc = check_flags(who, flags, kinds | PGX_CONFLICT_STAY | PGX_CONFLICT_VANISH)) return rc;
+    if (!(flags & kinds)) return fail_msg(PGX_E_INVALID, "%s: flags 0x%x name no conflict kind", who, flags);
+    if ((flags & PGX_CONFLICT_STAY) && (flags & PGX_CONFLICT_VANISH))
+        return fail_msg(PGX_E_INVALID, "%s: flags 0x%x set both PGX_CONFLICT_STAY and PGX_CONFLICT_VANISH", who, flags);
+    if (const int rc = check_aligned(who, layout == PGX_CONFLICT_PATHS_PLAN ? "a plan-layout paths" : "a cells-layout paths",
+                                     paths, layout == PGX_CONFLICT_PATHS_PLAN ? 4 : 2)) return rc;
+    if (const int rc = check_aligned(who, "first_step", first_step, 4)) return rc;
+    if (const int rc = check_aligned(who, "partner", partner, 4)) return rc;
+    if (const int rc = check_aligned(who, "count", count, 4)) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    pgx::ConflictParams p{state_view(e)};   // no cache, no allocation: one launch
+    p.paths = paths;
+    p.layout = layout;
+    p.steps = steps;
+    p.kinds = flags & kinds;
+    p.vanish = (flags & PGX_CONFLICT_VANISH) ? 1 : (flags & PGX_CONFLICT_STAY) ? 0 : e->cfg.on_target == PGX_ON_TARGET_FINISH;
+    p.first_step = first_step;
+    p.partner = partner;
+    p.kind = kind;
+    p.count = count;
+    PGX_HIP(pgx::launch_path_conflicts(p, (hipStream_t)stream));
+    return PGX_OK;
+}
+
 // ---- agent tokens (docs/SPEC.md S21) ------------------------------------------------------------------------
 int64_t pgx_agent_tokens_length(int32_t obs_radius, int32_t slots) {
     static const char who[] = "pgx_agent_tokens_length";

@@ -370,6 +370,23 @@ struct BlockingParams : CostToGoParams {   // `out` is not used
 // of `count` and the search launch)
 hipError_t launch_blocking(const BlockingParams& p, hipStream_t stream);
 
+// ---- path conflicts (pgx_path_conflicts.hip, docs/SPEC.md S26) ------------------------------------------------
+enum { CONFLICT_PATHS_PLAN = 0, CONFLICT_PATHS_CELLS = 1 };            // PGX_CONFLICT_PATHS_* (include/pogema_amd.h)
+enum { CONFLICT_VERTEX = 1, CONFLICT_EDGE = 2, CONFLICT_FOLLOW = 4 };  // PGX_CONFLICT_VERTEX / _EDGE / _FOLLOW
+struct ConflictParams : StateView {
+    const void* paths;       // PLAN: i32 [K][B][A][2]; CELLS: i16 [B][A][K][2]; unpadded (x, y), any values
+    int32_t layout;          // CONFLICT_PATHS_*
+    int32_t steps;           // K, 1..PGX_MAX_CONFLICT_STEPS: the step loop's trip count
+    int32_t kinds;           // the CONFLICT_* kinds that exist for this call, at least one
+    int32_t vanish;          // an agent takes no part after a step on its target
+    int32_t* first_step;     // [B][A] may be null
+    int32_t* partner;        // [B][A] may be null
+    uint8_t* kind;           // [B][A] may be null
+    int32_t* count;          // [B][A] may be null
+};
+// one launch; reads the state and `paths`, writes the four outputs only
+hipError_t launch_path_conflicts(const ConflictParams& p, hipStream_t stream);
+
 // ---- agent tokens (pgx_agent_tokens.hip): one row of token ids per agent (docs/SPEC.md S21) -------------------------
 struct TokenParams : CostToGoParams {   // `out` is not used
     int32_t slots;           // S, 1..PGX_MAX_TOKEN_SLOTS: the agent itself and S - 1 neighbours

@@ -204,6 +204,16 @@ class Pogema:
         planes, cells = (t[0].cpu().numpy() for t in self._vec.agent_forecasts(steps=steps, format="uint8"))
         return [(planes[i], [(int(x), int(y)) for x, y in cells[i]]) for i in range(planes.shape[0])]
 
+    def path_conflicts(self, paths=None, steps=3, kinds=("vertex", "edge"), arrived=None):
+        """Where K-step paths collide (VecPogema.path_conflicts) as a list of (first_step, partner, kinds, count) per
+        agent: ints, and the kinds of the first conflict as a tuple of names of pogema_amd.CONFLICT_KINDS.  `paths`: a
+        tensor as VecPogema.path_conflicts takes it (batch 1), or None for the agents' forecasts over `steps` steps."""
+        from ._lib import CONFLICT_KINDS
+        first, partner, kind, count = (t[0].cpu().numpy() for t in
+                                       self._vec.path_conflicts(paths=paths, steps=steps, kinds=kinds, arrived=arrived))
+        return [(int(first[i]), int(partner[i]), tuple(n for n, b in CONFLICT_KINDS.items() if int(kind[i]) & b), int(count[i]))
+                for i in range(first.shape[0])]
+
     def blocking(self, inflation=10, blockers="all"):
         """Which agents stand in the way of others (VecPogema.blocking) as two lists of ints: count[i], the number of
         agents that agent i blocks, and blocked_by[j], the number of agents that block agent j."""

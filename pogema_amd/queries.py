@@ -1,6 +1,6 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
 cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes, path-to-goal planes,
-agent forecasts, blocking counts, move outcomes, the policy input, the global state and the agent tokens.  Each is one C-ABI
+agent forecasts, blocking counts, path conflicts, move outcomes, the policy input, the global state and the agent tokens.  Each is one C-ABI
 call into caller-owned or fresh output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
 from __future__ import annotations
@@ -125,6 +125,31 @@ def parse_blockers(blockers="all"):
     if not isinstance(blockers, str) or blockers not in _lib.BLOCKING_BLOCKERS:
         raise ValueError(f"blockers must be one of {sorted(_lib.BLOCKING_BLOCKERS)}, got {blockers!r}")
     return _lib.BLOCKING_BLOCKERS[blockers]
+
+
+def parse_conflict_kinds(kinds=("vertex", "edge")):
+    """The `kinds` of path_conflicts() as the OR of their PGX_CONFLICT_* bits: a non-empty tuple or list of distinct names
+    of _lib.CONFLICT_KINDS, anything else is a ValueError that lists the vocabulary.  Needs no engine and no GPU."""
+    table = _lib.CONFLICT_KINDS
+    known = f"the kinds are {', '.join(repr(n) for n in table)}"
+    if isinstance(kinds, (str, bytes)) or not isinstance(kinds, (tuple, list)) or not kinds:
+        raise ValueError(f"kinds must be a non-empty tuple or list of conflict kinds, got {kinds!r}; {known}")
+    bits = 0
+    for k, name in enumerate(kinds):
+        if not isinstance(name, str) or name not in table:
+            raise ValueError(f"kinds[{k}] = {name!r} is not a conflict kind; {known}")
+        if bits & table[name]:
+            raise ValueError(f"kinds[{k}] = {name!r} is given twice; {known}")
+        bits |= table[name]
+    return bits
+
+
+def parse_conflict_arrived(arrived=None):
+    """The `arrived` of path_conflicts() as pgx_path_conflicts' arrival flag (0: the engine's on_target decides); anything
+    outside _lib.CONFLICT_ARRIVED is a ValueError that lists the vocabulary.  Needs no engine and no GPU."""
+    if not (arrived is None or isinstance(arrived, str)) or arrived not in _lib.CONFLICT_ARRIVED:
+        raise ValueError(f"arrived must be None, 'stay' or 'vanish', got {arrived!r}")
+    return _lib.CONFLICT_ARRIVED[arrived]
 
 
 class QueryMixin:
@@ -460,6 +485,58 @@ class QueryMixin:
         _lib.check(self._lib.pgx_blocking(self._handle, inflation, flags, count.data_ptr(), blocked_by.data_ptr(),
                                           self._stream()))
         return count, blocked_by
+
+    def path_conflicts(self, paths=None, steps: int = 3, kinds=("vertex", "edge"), arrived=None, out=None):
+        """Path conflicts (docs/SPEC.md S26): where K-step paths run into each other, per agent -- computed on the device
+        from the current state, the state the next step() reads, and `paths`; the call changes neither.
+        `paths`: K cells per agent as unpadded (x, y) in get_state()'s coordinates, contiguous, on this device, K in
+        1..MAX_CONFLICT_STEPS (256), in one of two layouts told apart by dtype:
+            int32 [K, batch, agents, 2]  -- pibt_plan()'s path_xy;
+            int16 [batch, agents, K, 2]  -- agent_forecasts()' cells.
+        None: agent_forecasts(steps, planes=False)'s cells, `steps` in 1..8 (with its cache contract and first-call
+        rule); `steps` is ignored when `paths` is given.  Cells are keys, not moves: the call does not judge whether a
+        path is legal, and a cell outside the map (a (-1, -1)) takes no part at its step.
+        With pos_0 the current cell and pos_h the path's cell h, an agent takes part at step h iff it is active, pos_h
+        lies inside the map and, under arrived="vanish", no earlier pos_h' (h' < h, the current cell included) is its
+        target.  Conflicts at h = 1..K between two agents that take part (for edge and follow: at h and at h - 1):
+            "vertex"  both are on one cell at h;
+            "edge"    they change places between h - 1 and h;
+            "follow"  this agent moves to the cell the other one leaves for a third cell (on the follower only).
+        `kinds`: a non-empty tuple or list of those names: the kinds that exist for this call.  "follow" is opt-in: only
+        the `priority` and `block_both` collision systems revert such moves.
+        `arrived`: "stay", "vanish" or None: "vanish" iff the engine's on_target is "finish", pibt_plan()'s rule.
+        Returns (first_step int32 [batch, agents]: the first step with a conflict of this agent, -1 if none;
+                 partner int32 [batch, agents]: the lowest agent it conflicts with at that step, -1 if none;
+                 kind uint8 [batch, agents]: the OR of pogema_amd.CONFLICT_KINDS' bits over its conflicts at that step;
+                 count int32 [batch, agents]: its conflicts (pairs of a step and another agent) over all K steps).
+        An inactive agent gets -1, -1, 0, 0.  One launch that reads no distance field and allocates nothing on the engine
+        side: with `paths` given it is stream-ordered, needs no host sync and is capturable in a HIP graph from the first
+        call.  `out=(first_step, partner, kind, count)`: caller-owned contiguous tensors of those dtypes and shapes on
+        this device."""
+        B, A = self.batch, self.num_agents
+        flags = parse_conflict_kinds(kinds) | parse_conflict_arrived(arrived)
+        if paths is None:
+            _, paths = self.agent_forecasts(parse_forecast_steps(steps), planes=False)
+        if not isinstance(paths, torch.Tensor) or paths.dtype not in (torch.int32, torch.int16):
+            raise TypeError("paths must be an int32 [K, batch, agents, 2] or an int16 [batch, agents, K, 2] tensor, got "
+                            f"{paths.dtype if isinstance(paths, torch.Tensor) else type(paths).__name__}")
+        plan = paths.dtype == torch.int32
+        K = paths.shape[0 if plan else 2] if paths.dim() == 4 else 0
+        want = (K, B, A, 2) if plan else (B, A, K, 2)
+        if not (1 <= K <= _lib.MAX_CONFLICT_STEPS and tuple(paths.shape) == want and paths.is_contiguous()
+                and paths.device == torch.device(self.device)):
+            raise ValueError(f"paths must be a contiguous {'int32' if plan else 'int16'} tensor of shape "
+                             f"{('K', B, A, 2) if plan else (B, A, 'K', 2)} with K in 1..{_lib.MAX_CONFLICT_STEPS} on "
+                             f"{self.device}, got shape {tuple(paths.shape)} on {paths.device}")
+        first_step, partner, kind, count = _split(out, ("first_step", "partner", "kind", "count"))
+        first_step = query_output("out[first_step]", first_step, torch.int32, (B, A), self.device)
+        partner = query_output("out[partner]", partner, torch.int32, (B, A), self.device)
+        kind = query_output("out[kind]", kind, torch.uint8, (B, A), self.device)
+        count = query_output("out[count]", count, torch.int32, (B, A), self.device)
+        _lib.check(self._lib.pgx_path_conflicts(
+            self._handle, paths.data_ptr(), _lib.CONFLICT_PATHS_PLAN if plan else _lib.CONFLICT_PATHS_CELLS, K, flags,
+            first_step.data_ptr(), partner.data_ptr(), kind.data_ptr(), count.data_ptr(), self._stream()))
+        return first_step, partner, kind, count
 
     def move_outcomes(self, actions, out=None):
         """Move outcomes (docs/SPEC.md S17): what the move phase of step(actions) would do to every agent and why a move
