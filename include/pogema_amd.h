@@ -395,8 +395,8 @@ int pgx_cost_to_go(pgx_env* env, int32_t flags, int32_t* out, void* stream);
  * rounded up to a multiple of 16 + 4 * B * A (target tags) + 4 * B * H * ceil(W / 32) (map copies).  Returns the status
  * code of pgx_check_config for a configuration it refuses. */
 int64_t pgx_cost_to_go_bytes(const pgx_config* cfg);
-/* Distance fields pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_goal_directions and pgx_shield_actions have
- * built since the handle was created (0 before the first call of any of them).  Synchronises `stream`. */
+/* Distance fields pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_pibt_swap_plan, pgx_goal_directions and
+ * pgx_shield_actions have built since the handle was created (0 before the first call of any of them).  Synchronises `stream`. */
 int64_t pgx_cost_to_go_builds(pgx_env* env, void* stream);
 
 /* Neighbour lists (docs/SPEC.md S12), read from the current device state -- the state the next pgx_step reads, which
@@ -494,6 +494,21 @@ int pgx_pibt_swap_actions(pgx_env* env, int32_t flags, const int32_t* priority, 
 #define PGX_MAX_PLAN_HORIZON 256
 int pgx_pibt_plan(pgx_env* env, int32_t flags, int32_t horizon, const int32_t* priority, void* actions,
                   int32_t action_dtype, int32_t* path_xy, int32_t* arrival, int32_t* priority_out, void* stream);
+
+/* Multi-step planner with the swap operation (docs/SPEC.md S27): pgx_pibt_plan's lookahead -- the private copy of the
+ * positions, the targets and distance fields held for all steps, the planned / arrival / priority rules, the outputs --
+ * with pgx_pibt_swap_actions' planner in place of pgx_pibt_actions' at every step.  The swap rule is evaluated on the
+ * positions and the planned agents of the step it plans: an agent that stopped being planned under
+ * PGX_ON_TARGET_FINISH stands in nobody's way, is nobody's partner and parks in no dead end.  A corridor walk takes at
+ * most PGX_SWAP_MAX_WALK steps in every step of the lookahead; the cap is part of the semantics.  pgx_pibt_actions'
+ * guarantees hold for every step.  With horizon = 1, actions and path_xy are pgx_pibt_swap_actions' outputs; in an env
+ * in which the rule reverses no agent's candidates at any step, all four outputs are pgx_pibt_plan's.
+ *   flags, horizon, priority, actions, action_dtype, path_xy, arrival, priority_out   as in pgx_pibt_plan
+ * What pgx_pibt_plan says about pgx_rollout following path_xy holds here too.  Cache, allocation, capture (ONE refresh
+ * per call whatever K is, then one more launch), status codes and the order of the checks (arguments before the handle:
+ * no device needed) are pgx_pibt_plan's. */
+int pgx_pibt_swap_plan(pgx_env* env, int32_t flags, int32_t horizon, const int32_t* priority, void* actions,
+                       int32_t action_dtype, int32_t* path_xy, int32_t* arrival, int32_t* priority_out, void* stream);
 
 /* Collision shielding (docs/SPEC.md S15): pgx_pibt_actions' planner -- the same planned agents, serving order
  * (-priority, index), priority inheritance, backtracking, outputs and guarantees -- with every agent's candidate cells

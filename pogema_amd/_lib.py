@@ -118,7 +118,7 @@ EXPORTED_SYMBOLS = (
     "pgx_cost_to_go", "pgx_cost_to_go_bytes", "pgx_cost_to_go_builds", "pgx_visible_agents", "pgx_pibt_actions",
     "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan", "pgx_move_outcomes",
     "pgx_policy_input", "pgx_copy_envs", "pgx_global_state", "pgx_global_state_check",
-    "pgx_agent_tokens", "pgx_agent_tokens_length", "pgx_goal_paths", "pgx_pibt_swap_actions",
+    "pgx_agent_tokens", "pgx_agent_tokens_length", "pgx_goal_paths", "pgx_pibt_swap_actions", "pgx_pibt_swap_plan",
     "pgx_agent_forecasts", "pgx_blocking", "pgx_path_conflicts",
 )
 
@@ -243,6 +243,8 @@ def load() -> C.CDLL:
     lib.pgx_pibt_swap_actions.restype = C.c_int
     lib.pgx_pibt_plan.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.pgx_pibt_plan.restype = C.c_int
+    lib.pgx_pibt_swap_plan.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
+    lib.pgx_pibt_swap_plan.restype = C.c_int
     lib.pgx_goal_directions.argtypes = [vp, i32, vp, i32, vp]
     lib.pgx_goal_directions.restype = C.c_int
     lib.pgx_shield_actions.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp]

@@ -1092,7 +1092,7 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
 }
 
 // The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
-// first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_goal_directions,
+// first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_pibt_swap_plan, pgx_goal_directions,
 // pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE, pgx_policy_input with a direction channel, pgx_agent_tokens, pgx_goal_paths, pgx_agent_forecasts, pgx_blocking).  `who` names that entry point in the error messages.
 static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p) {
     const pgx_config& c = e->cfg;
@@ -1194,10 +1194,10 @@ int pgx_pibt_swap_actions(pgx_env* e, int32_t flags, const int32_t* priority, vo
     return PGX_OK;
 }
 
-// ---- multi-step planner (docs/SPEC.md S16) ----------------------------------------------------------------
-int pgx_pibt_plan(pgx_env* e, int32_t flags, int32_t horizon, const int32_t* priority, void* actions, int32_t action_dtype,
-                  int32_t* path_xy, int32_t* arrival, int32_t* priority_out, void* stream) {
-    static const char who[] = "pgx_pibt_plan";
+// ---- multi-step planner (docs/SPEC.md S16), and the same lookahead with the swap operation (S27) -----------------
+static int pibt_plan_entry(const char* who, bool swap, pgx_env* e, int32_t flags, int32_t horizon, const int32_t* priority,
+                           void* actions, int32_t action_dtype, int32_t* path_xy, int32_t* arrival, int32_t* priority_out,
+                           void* stream) {
     // the argument checks come first and need no device
     if (!actions) return fail_msg(PGX_E_INVALID, "%s: actions is null", who);
     if (const int rc = check_flags(who, flags, PGX_PLAN_FIXED_PRIORITY)) return rc;
@@ -1229,8 +1229,20 @@ int pgx_pibt_plan(pgx_env* e, int32_t flags, int32_t horizon, const int32_t* pri
     p.path_xy = path_xy;
     p.arrival = arrival;
     p.priority_out = priority_out;
-    PGX_HIP(pgx::launch_pibt_plan(p, s));
+    PGX_HIP(swap ? pgx::launch_pibt_swap_plan(p, s) : pgx::launch_pibt_plan(p, s));
     return PGX_OK;
+}
+
+int pgx_pibt_plan(pgx_env* e, int32_t flags, int32_t horizon, const int32_t* priority, void* actions, int32_t action_dtype,
+                  int32_t* path_xy, int32_t* arrival, int32_t* priority_out, void* stream) {
+    return pibt_plan_entry("pgx_pibt_plan", false, e, flags, horizon, priority, actions, action_dtype, path_xy, arrival,
+                           priority_out, stream);
+}
+
+int pgx_pibt_swap_plan(pgx_env* e, int32_t flags, int32_t horizon, const int32_t* priority, void* actions,
+                       int32_t action_dtype, int32_t* path_xy, int32_t* arrival, int32_t* priority_out, void* stream) {
+    return pibt_plan_entry("pgx_pibt_swap_plan", true, e, flags, horizon, priority, actions, action_dtype, path_xy, arrival,
+                           priority_out, stream);
 }
 
 // ---- collision shielding (docs/SPEC.md S15) ---------------------------------------------------------------

@@ -462,6 +462,8 @@ struct PibtPlanParams : PibtParams {   // `actions` is [horizon][B][A]; `next_xy
     int32_t* priority_out;   // [B][A], may be null
 };
 hipError_t launch_pibt_plan(const PibtPlanParams& p, hipStream_t stream);
+// the same lookahead over the planner with the swap operation (pgx_pibt_swap_horizon.hip, docs/SPEC.md S27)
+hipError_t launch_pibt_swap_plan(const PibtPlanParams& p, hipStream_t stream);
 
 // ---- collision shielding (pgx_shield.hip): the planner over the caller's action scores ------------------------------
 enum { SCORES_F32 = 0, SCORES_F16 = 1, SCORES_BF16 = 2 };  // PGX_SCORES_* (include/pogema_amd.h)

@@ -267,15 +267,15 @@ class Pogema:
         actions, _ = vec.pibt_actions(priority=priority, swap=swap)
         return [int(a) for a in actions[0].cpu().numpy()]
 
-    def pibt_plan(self, horizon, priority=None):
+    def pibt_plan(self, horizon, priority=None, swap=False):
         """The cooperative planner's actions for the next `horizon` steps (VecPogema.pibt_plan), as one list per step
         for step().  `priority`: one integer per agent for the first step, None = all equal; they grow inside the
-        lookahead."""
+        lookahead.  `swap=True`: every step plans with the swap operation (docs/SPEC.md S27)."""
         import torch
         vec = self._vec
         if priority is not None:
             priority = torch.as_tensor(np.asarray(priority, dtype=np.int64)[None], device=vec.device)
-        actions = vec.pibt_plan(horizon, priority=priority)[0]
+        actions = vec.pibt_plan(horizon, priority=priority, swap=swap)[0]
         return [[int(a) for a in row] for row in actions[:, 0].cpu().numpy()]
 
     def shield_actions(self, scores, priority=None):

@@ -14,8 +14,10 @@ class PibtPolicy:
     `plan(horizon)` -> (actions, path_xy, arrival) for `env.rollout`: the same priorities grown inside the lookahead
     (VecPogema.pibt_plan, docs/SPEC.md S16); no `update()` is needed between a plan and the next.
     `PibtPolicy(env, swap=True)`: act() plans with the swap operation (VecPogema.pibt_actions(swap=True), docs/SPEC.md
-    S23), which clears the dead ends and corridors the plain rule livelocks in; act(scores=...) is unchanged, and plan()
-    raises: the multi-step planner has no swap rule yet."""
+    S23), which clears the dead ends and corridors the plain rule livelocks in; act(scores=...) is unchanged.
+    `plan(horizon, swap=True)` plans with the swap operation at every step (VecPogema.pibt_plan(swap=True), S27) and
+    `plan(horizon, swap=False)` without, whatever the policy was built with.  Without the keyword a policy built
+    without swap plans without it, and one built with swap=True raises: the choice has to be made in the call."""
 
     def __init__(self, env, swap=False):
         if not isinstance(swap, bool):
@@ -34,18 +36,26 @@ class PibtPolicy:
             return self.env.pibt_actions(priority=self.priority, dtype=dtype, out=out, swap=self.swap)
         return self.env.shield_actions(scores, priority=self.priority, tie_break=tie_break, dtype=dtype, out=out)
 
-    def plan(self, horizon, dtype=torch.int64, out=None):
+    def plan(self, horizon, dtype=torch.int64, out=None, *, swap=None):
         """`horizon` steps planned ahead from the current state under `self.priority`; the priorities the lookahead
         ends with replace it, so that the next plan() or act() after `env.rollout(actions)` continues where this one
         stopped.  The plan does not know when an episode ends: where the rollout reports `episode_done` for an env (its
         time limit, or every agent finished), zero that env's row of `self.priority` before planning again, as
         `update(rewards, episode_done)` does.  `out=(actions, path_xy, arrival, priority)` as VecPogema.pibt_plan takes
-        it."""
-        if self.swap:
-            raise ValueError("plan() is not available on a PibtPolicy(env, swap=True): the multi-step planner "
-                             "(pibt_plan) has no swap rule yet; use act(), or a policy without swap")
+        it.  `swap`: True plans with the swap operation (docs/SPEC.md S27), False without; None leaves it to the
+        policy -- without swap for one built without it, an error for one built with swap=True."""
+        if swap is not None and not isinstance(swap, bool):
+            raise TypeError(f"swap must be a bool or None, got {type(swap).__name__}")
+        if swap is None:
+            if self.swap:
+                raise ValueError("plan() on a PibtPolicy(env, swap=True): the multi-step planner (pibt_plan) applies "
+                                 "no swap rule unless asked: call plan(horizon, swap=True), or plan(horizon, "
+                                 "swap=False) for the plain lookahead")
+            keyword = {}                      # an env whose pibt_plan has no such keyword plans as before
+        else:
+            keyword = {"swap": swap}
         actions, path_xy, arrival, self.priority = self.env.pibt_plan(horizon, priority=self.priority, dtype=dtype,
-                                                                     out=out)
+                                                                     out=out, **keyword)
         return actions, path_xy, arrival
 
     def copy_envs(self, src, dst, *, cache: bool = True, validate: bool = True) -> None:

@@ -272,7 +272,7 @@ class QueryMixin:
                         self._ACTION_CODE[actions.dtype], next_xy.data_ptr(), self._stream()))
         return actions, next_xy
 
-    def pibt_plan(self, horizon, priority=None, growing: bool = True, dtype=torch.int64, out=None):
+    def pibt_plan(self, horizon, priority=None, growing: bool = True, dtype=torch.int64, out=None, *, swap=False):
         """Multi-step planner (docs/SPEC.md S16): pibt_actions()' planner iterated `horizon` times in one launch, on a
         private copy of the positions -- computed on the device from the current state, which the call leaves untouched.
         Step h plans from the cells step h - 1 sent the agents to; the targets are held for the whole lookahead.  Under
@@ -293,8 +293,14 @@ class QueryMixin:
         `horizon`: an integer in 1..MAX_PLAN_HORIZON (256).  `priority`: as in pibt_actions().
         Shares cost_to_go()'s cache under pibt_actions()' rules, with one refresh per call whatever the horizon is.
         `out=(actions, path_xy, arrival, priority)`: caller-owned contiguous tensors on this device (actions int8 /
-        int32 / int64, the others int32)."""
+        int32 / int64, the others int32).
+        `swap=True`: every step plans with the swap operation (docs/SPEC.md S27, pgx_pibt_swap_plan) -- the rule of
+        pibt_actions(swap=True), evaluated on the positions and the planned agents of the step it plans, which takes a
+        plan through the corridors and dead ends the plain lookahead livelocks in.  Same arguments, outputs, guarantees
+        and cache rules; with horizon = 1, actions[0] and path_xy[0] are pibt_actions(swap=True)'s outputs."""
         B, A = self.batch, self.num_agents
+        if not isinstance(swap, (bool, np.bool_)):
+            raise TypeError(f"swap must be a bool, got {type(swap).__name__}")
         if (isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer))
                 or not 1 <= horizon <= _lib.MAX_PLAN_HORIZON):
             raise ValueError(f"horizon must be an integer in 1..{_lib.MAX_PLAN_HORIZON}, got {horizon!r}")
@@ -305,10 +311,11 @@ class QueryMixin:
         path_xy = query_output("out[path_xy]", path_xy, torch.int32, (K, B, A, 2), self.device)
         arrival = query_output("out[arrival]", arrival, torch.int32, (B, A), self.device)
         priority_out = query_output("out[priority]", priority_out, torch.int32, (B, A), self.device)
-        _lib.check(self._lib.pgx_pibt_plan(self._handle, 0 if growing else _lib.PLAN_FIXED_PRIORITY, K,
-                                           priority.data_ptr() if priority is not None else None, actions.data_ptr(),
-                                           self._ACTION_CODE[actions.dtype], path_xy.data_ptr(), arrival.data_ptr(),
-                                           priority_out.data_ptr(), self._stream()))
+        call = self._lib.pgx_pibt_swap_plan if swap else self._lib.pgx_pibt_plan
+        _lib.check(call(self._handle, 0 if growing else _lib.PLAN_FIXED_PRIORITY, K,
+                        priority.data_ptr() if priority is not None else None, actions.data_ptr(),
+                        self._ACTION_CODE[actions.dtype], path_xy.data_ptr(), arrival.data_ptr(),
+                        priority_out.data_ptr(), self._stream()))
         return actions, path_xy, arrival, priority_out
 
     def shield_actions(self, scores, priority=None, tie_break=None, dtype=torch.int64, out=None):
