@@ -395,8 +395,8 @@ int pgx_cost_to_go(pgx_env* env, int32_t flags, int32_t* out, void* stream);
  * rounded up to a multiple of 16 + 4 * B * A (target tags) + 4 * B * H * ceil(W / 32) (map copies).  Returns the status
  * code of pgx_check_config for a configuration it refuses. */
 int64_t pgx_cost_to_go_bytes(const pgx_config* cfg);
-/* Distance fields pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_pibt_swap_plan, pgx_goal_directions and
- * pgx_shield_actions have built since the handle was created (0 before the first call of any of them).  Synchronises `stream`. */
+/* Distance fields pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_pibt_swap_plan, pgx_whca_plan, pgx_goal_directions
+ * and pgx_shield_actions have built since the handle was created (0 before the first call of any of them).  Synchronises `stream`. */
 int64_t pgx_cost_to_go_builds(pgx_env* env, void* stream);
 
 /* Neighbour lists (docs/SPEC.md S12), read from the current device state -- the state the next pgx_step reads, which
@@ -509,6 +509,42 @@ int pgx_pibt_plan(pgx_env* env, int32_t flags, int32_t horizon, const int32_t* p
  * no device needed) are pgx_pibt_plan's. */
 int pgx_pibt_swap_plan(pgx_env* env, int32_t flags, int32_t horizon, const int32_t* priority, void* actions,
                        int32_t action_dtype, int32_t* path_xy, int32_t* arrival, int32_t* priority_out, void* stream);
+
+/* Windowed cooperative A* against a reservation table (WHCA*, docs/SPEC.md S28): prioritized planning in space-time,
+ * read from the current device state, which the call does not change.  The planned agents (bit 0 of is_active) of an env
+ * are served in the order (-priority, index).  Each gets a path of K = horizon steps over its own cell and the free
+ * cells of the map that avoids every cell (vertex reservation) and every head-on move (edge reservation) of the agents
+ * served before it: layer R_h is the set of cells it can stand on after h steps, R_0 its own cell.  Under
+ * PGX_ON_TARGET_FINISH the search ends at the first layer that holds the target, and the agent reserves nothing after
+ * that step; otherwise it ends at the cell of R_K with the smallest (distance to the target, row-major index) -- the
+ * distance is pgx_cost_to_go's field of the agent, the Manhattan distance to its own cell when the target cannot be
+ * reached.  The path is read back from the end, the lowest action first, so an agent reaches its end cell as early as
+ * the reservations allow and waits there.  An agent with an empty layer has FAILED: it stays on its cell, which it
+ * reserves for the whole window, so that later agents plan around it.  Agents that are not planned get action 0, keep
+ * their cell and reserve nothing; cells of agents not served yet are not reserved.  Prioritized planning is incomplete:
+ * `failed` is how it says so, other priorities are the remedy.
+ *   flags     reserved, must be 0
+ *   horizon   K, 1..PGX_MAX_WHCA_HORIZON (the cap is part of the semantics: the box an agent can reach is 63 x 63 cells)
+ *   priority  device i32 [batch, agents]; NULL: every priority is 0 (index order)
+ *   actions   device [K, batch, agents] of action_dtype (PGX_ACTION_*), the layout pgx_rollout reads.  Must not be NULL.
+ *   path_xy   device i32 [K, batch, agents, 2]: the cell after step h + 1, unpadded (row, col) -- pgx_pibt_plan's layout,
+ *             what pgx_path_conflicts takes with PGX_CONFLICT_PATHS_PLAN.  May be NULL.
+ *   arrival   device i32 [batch, agents]: for a planned agent the smallest h in 0..K at which its path stands on its
+ *             target, -1 when there is none; -1 for every other agent.  May be NULL.
+ *   failed    device i32 [batch, agents]: 1 for a failed agent, else 0.  May be NULL.
+ * From a state in which the planned agents stand on distinct cells, no two planned agents that did not fail meet in a
+ * cell or swap cells at any step (an agent that ended on its target under PGX_ON_TARGET_FINISH takes no part after
+ * that step).  In an env without a failed agent, under PGX_COLLISION_SOFT with PGX_ON_TARGET_FINISH or
+ * PGX_ON_TARGET_NOTHING, a pgx_rollout of `actions` puts every agent on path_xy[h] after step h for as long as the env's
+ * episode lasts; pgx_pibt_plan's caveats for PGX_ON_TARGET_RESTART and the other collision systems apply.
+ * Shares pgx_cost_to_go's distance-field cache under pgx_pibt_plan's rules: ONE refresh per call, then one more launch;
+ * whichever entry point that uses the cache is called first allocates it -- inside a graph capture that first call
+ * returns PGX_E_STATE.  Afterwards asynchronous on `stream`, no host sync, capturable in a HIP graph.  PGX_E_INVALID for
+ * a NULL `actions`, non-zero flags, a horizon outside its range, a bad action_dtype or a misaligned pointer (checked
+ * before the handle: no device needed); PGX_E_STATE before the first reset, like pgx_step. */
+#define PGX_MAX_WHCA_HORIZON 31
+int pgx_whca_plan(pgx_env* env, int32_t flags, int32_t horizon, const int32_t* priority, void* actions,
+                  int32_t action_dtype, int32_t* path_xy, int32_t* arrival, int32_t* failed, void* stream);
 
 /* Collision shielding (docs/SPEC.md S15): pgx_pibt_actions' planner -- the same planned agents, serving order
  * (-priority, index), priority inheritance, backtracking, outputs and guarantees -- with every agent's candidate cells

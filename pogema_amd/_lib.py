@@ -71,6 +71,7 @@ MAX_CONFLICT_STEPS = 256  # PGX_MAX_CONFLICT_STEPS: steps of one pgx_path_confli
 SHIELD_TIE_BREAKS = {None: 0, "distance": 1}  # flags of pgx_shield_actions (PGX_SHIELD_TIE_DISTANCE)
 MAX_PLAN_HORIZON = 256  # PGX_MAX_PLAN_HORIZON: steps of one pgx_pibt_plan
 PLAN_FIXED_PRIORITY = 1  # PGX_PLAN_FIXED_PRIORITY: flag of pgx_pibt_plan
+MAX_WHCA_HORIZON = 31  # PGX_MAX_WHCA_HORIZON: the window of one pgx_whca_plan (docs/SPEC.md S28)
 SWAP_MAX_WALK = 2048  # PGX_SWAP_MAX_WALK: steps of a corridor walk of pgx_pibt_swap_actions (docs/SPEC.md S23)
 # PGX_OUTCOME_*: the codes of pgx_move_outcomes, index = code (docs/SPEC.md S17)
 OUTCOMES = ("STAY", "MOVED", "OBSTACLE", "SWAP", "OCCUPIED", "FOLLOW", "CONTESTED")
@@ -119,7 +120,7 @@ EXPORTED_SYMBOLS = (
     "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan", "pgx_move_outcomes",
     "pgx_policy_input", "pgx_copy_envs", "pgx_global_state", "pgx_global_state_check",
     "pgx_agent_tokens", "pgx_agent_tokens_length", "pgx_goal_paths", "pgx_pibt_swap_actions", "pgx_pibt_swap_plan",
-    "pgx_agent_forecasts", "pgx_blocking", "pgx_path_conflicts",
+    "pgx_agent_forecasts", "pgx_blocking", "pgx_path_conflicts", "pgx_whca_plan",
 )
 
 
@@ -245,6 +246,8 @@ def load() -> C.CDLL:
     lib.pgx_pibt_plan.restype = C.c_int
     lib.pgx_pibt_swap_plan.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.pgx_pibt_swap_plan.restype = C.c_int
+    lib.pgx_whca_plan.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
+    lib.pgx_whca_plan.restype = C.c_int
     lib.pgx_goal_directions.argtypes = [vp, i32, vp, i32, vp]
     lib.pgx_goal_directions.restype = C.c_int
     lib.pgx_shield_actions.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp]

@@ -465,6 +465,21 @@ hipError_t launch_pibt_plan(const PibtPlanParams& p, hipStream_t stream);
 // the same lookahead over the planner with the swap operation (pgx_pibt_swap_horizon.hip, docs/SPEC.md S27)
 hipError_t launch_pibt_swap_plan(const PibtPlanParams& p, hipStream_t stream);
 
+// ---- windowed cooperative A* (pgx_whca.hip, docs/SPEC.md S28): space-time paths against a reservation table ----------
+struct WhcaParams : StateView {
+    int32_t action_dtype;    // PGX_ACTION_*
+    int32_t cell_bytes;      // of `field`: CostToGoLayout::cell_bytes
+    int32_t horizon;         // K, 1..PGX_MAX_WHCA_HORIZON: the window of the search
+    int32_t finish;          // on_target = finish: a search ends on the target, and the agent reserves nothing afterwards
+    const void* field;       // [B][A][H*W] the refreshed distance fields of the cost-to-go cache
+    const int32_t* priority; // [B][A], null: every priority is 0
+    void* actions;           // [K][B][A] of action_dtype
+    int32_t* path_xy;        // [K][B][A][2] unpadded, may be null
+    int32_t* arrival;        // [B][A], may be null
+    int32_t* failed;         // [B][A], may be null
+};
+hipError_t launch_whca(const WhcaParams& p, hipStream_t stream);
+
 // ---- collision shielding (pgx_shield.hip): the planner over the caller's action scores ------------------------------
 enum { SCORES_F32 = 0, SCORES_F16 = 1, SCORES_BF16 = 2 };  // PGX_SCORES_* (include/pogema_amd.h)
 struct ShieldParams : PibtParams {   // `field` is null without `tie_distance`

@@ -278,6 +278,17 @@ class Pogema:
         actions = vec.pibt_plan(horizon, priority=priority, swap=swap)[0]
         return [[int(a) for a in row] for row in actions[:, 0].cpu().numpy()]
 
+    def whca_plan(self, horizon, priority=None):
+        """Windowed cooperative A* paths for the next `horizon` steps (VecPogema.whca_plan), as one list of actions per
+        step for step().  `priority`: one integer per agent, None = all equal; an agent the planner could not serve
+        stays on its cell (VecPogema.whca_plan reports which)."""
+        import torch
+        vec = self._vec
+        if priority is not None:
+            priority = torch.as_tensor(np.asarray(priority, dtype=np.int64)[None], device=vec.device)
+        actions = vec.whca_plan(horizon, priority=priority)[0]
+        return [[int(a) for a in row] for row in actions[:, 0].cpu().numpy()]
+
     def shield_actions(self, scores, priority=None):
         """A policy's action scores made jointly collision-free (VecPogema.shield_actions), as a list for step().
         `scores`: array-like [agents, 5], one score per agent and action, higher is better; `priority`: one integer per

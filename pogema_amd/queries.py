@@ -1,5 +1,5 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
-cooperative planner and its multi-step lookahead, collision shielding, direction-to-goal planes, path-to-goal planes,
+cooperative planner and its multi-step lookahead, windowed cooperative A*, collision shielding, direction-to-goal planes, path-to-goal planes,
 agent forecasts, blocking counts, path conflicts, move outcomes, the policy input, the global state and the agent tokens.  Each is one C-ABI
 call into caller-owned or fresh output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
@@ -199,7 +199,7 @@ class QueryMixin:
 
     @property
     def cost_to_go_builds(self) -> int:
-        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), goal_directions(), goal_paths(), agent_forecasts(), blocking(), agent_tokens() and
+        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), whca_plan(), goal_directions(), goal_paths(), agent_forecasts(), blocking(), agent_tokens() and
         shield_actions(tie_break="distance") have built since this env was created (synchronises the stream)."""
         n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
         if n < 0:
@@ -317,6 +317,47 @@ class QueryMixin:
                         self._ACTION_CODE[actions.dtype], path_xy.data_ptr(), arrival.data_ptr(),
                         priority_out.data_ptr(), self._stream()))
         return actions, path_xy, arrival, priority_out
+
+    def whca_plan(self, horizon, priority=None, dtype=torch.int64, out=None):
+        """Windowed cooperative A* against a reservation table (WHCA*, docs/SPEC.md S28): prioritized planning in
+        space-time, computed on the device from the current state, which the call leaves untouched.  The active agents
+        of an env are served by (-priority, index); each gets a `horizon`-step path over the free cells that avoids
+        every cell and every head-on move of the agents served before it.  Under on_target="finish" a path ends at the
+        first step that can reach the target, and the agent reserves nothing afterwards; otherwise it ends at the cell
+        reachable in `horizon` steps that is nearest to the target (cost_to_go()'s field, ties in row-major order), as
+        early as the reservations allow, and waits there.  An agent whose search runs out of cells has failed: it
+        stays on its cell, reserves it for the whole window, and later agents plan around it.  Returns
+            (actions [horizon, batch, agents] of `dtype`: what rollout(actions) takes;
+             path_xy int32 [horizon, batch, agents, 2]: the cell after each step, unpadded (row, col) -- pibt_plan()'s
+                 layout, what path_conflicts() takes;
+             arrival int32 [batch, agents]: the first h in 0..horizon at which the path stands on the target, -1 when
+                 it does not, and for every inactive agent;
+             failed int32 [batch, agents]: 1 for a failed agent, else 0).
+        From a state with the active agents on distinct cells, no two agents that did not fail meet in a cell or swap
+        cells at any step; in an env without a failed agent, under collision_system="soft" with on_target "finish" or
+        "nothing", rollout(actions) puts every agent on path_xy[h] after step h until the env's episode ends.
+        pibt_plan()'s caveats apply to "restart" (exact up to the first arrival) and to "priority" / "block_both"
+        (exact up to the first reverted move).  Prioritized planning is incomplete: `failed` says where, and other
+        priorities on the next call are the remedy.
+        `horizon`: an integer in 1..MAX_WHCA_HORIZON (31).  `priority`: as in pibt_actions().
+        Shares cost_to_go()'s cache under pibt_actions()' rules, with one refresh per call.
+        `out=(actions, path_xy, arrival, failed)`: caller-owned contiguous tensors on this device (actions int8 /
+        int32 / int64, the others int32)."""
+        B, A = self.batch, self.num_agents
+        if (isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer))
+                or not 1 <= horizon <= _lib.MAX_WHCA_HORIZON):
+            raise ValueError(f"horizon must be an integer in 1..{_lib.MAX_WHCA_HORIZON}, got {horizon!r}")
+        K = int(horizon)
+        priority = self._priority(priority)
+        actions, path_xy, arrival, failed = _split(out, ("actions", "path_xy", "arrival", "failed"))
+        actions = query_output("out[actions]", actions, self._action_dtypes(dtype, actions), (K, B, A), self.device)
+        path_xy = query_output("out[path_xy]", path_xy, torch.int32, (K, B, A, 2), self.device)
+        arrival = query_output("out[arrival]", arrival, torch.int32, (B, A), self.device)
+        failed = query_output("out[failed]", failed, torch.int32, (B, A), self.device)
+        _lib.check(self._lib.pgx_whca_plan(self._handle, 0, K, priority.data_ptr() if priority is not None else None,
+                                           actions.data_ptr(), self._ACTION_CODE[actions.dtype], path_xy.data_ptr(),
+                                           arrival.data_ptr(), failed.data_ptr(), self._stream()))
+        return actions, path_xy, arrival, failed
 
     def shield_actions(self, scores, priority=None, tie_break=None, dtype=torch.int64, out=None):
         """Collision shielding (docs/SPEC.md S15): pibt_actions()' planner with every agent's candidate cells ordered by
