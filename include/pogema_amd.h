@@ -395,7 +395,7 @@ int pgx_cost_to_go(pgx_env* env, int32_t flags, int32_t* out, void* stream);
  * rounded up to a multiple of 16 + 4 * B * A (target tags) + 4 * B * H * ceil(W / 32) (map copies).  Returns the status
  * code of pgx_check_config for a configuration it refuses. */
 int64_t pgx_cost_to_go_bytes(const pgx_config* cfg);
-/* Distance fields pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_pibt_swap_plan, pgx_whca_plan, pgx_goal_directions
+/* Distance fields pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_pibt_swap_plan, pgx_whca_plan, pgx_repair_plan, pgx_goal_directions
  * and pgx_shield_actions have built since the handle was created (0 before the first call of any of them).  Synchronises `stream`. */
 int64_t pgx_cost_to_go_builds(pgx_env* env, void* stream);
 
@@ -545,6 +545,42 @@ int pgx_pibt_swap_plan(pgx_env* env, int32_t flags, int32_t horizon, const int32
 #define PGX_MAX_WHCA_HORIZON 31
 int pgx_whca_plan(pgx_env* env, int32_t flags, int32_t horizon, const int32_t* priority, void* actions,
                   int32_t action_dtype, int32_t* path_xy, int32_t* arrival, int32_t* failed, void* stream);
+
+/* Plan repair (docs/SPEC.md S29): pgx_whca_plan for chosen agents, around the paths the others keep.  Read from the
+ * current device state, which the call does not change.  For a planned agent i, given_i[0] is its cell and given_i[h] =
+ * paths[h - 1, b, i].  Its given path is a WALK when, scanning h = 1, 2, ..., every given_i[h] lies inside the map (this
+ * is checked first: the cells may be any int32), is no obstacle and differs from given_i[h - 1] by one of the five moves,
+ * stay included.  Under PGX_ON_TARGET_FINISH the scan stops at the first h >= 1 with given_i[h] on the agent's target:
+ * that h is the agent's last step and whatever `paths` holds after it is ignored; otherwise the last step is K.
+ * A planned agent with replan == 0 (or replan NULL) whose given path is a walk is KEPT: its cells are the given ones up
+ * to its last step and the last of them from there on.  Every other planned agent is REPLANNED.  All kept agents are
+ * entered into the reservation table first -- the cell of every step up to the last, every real move; conflicts among
+ * them are neither looked for nor resolved, that is pgx_path_conflicts' job.  Then the replanned agents are served in the
+ * order (-priority, index), each exactly as pgx_whca_plan serves an agent, against the kept agents and the replanned
+ * agents served before it.  Agents that are not planned are treated as by pgx_whca_plan; their `paths` rows are ignored.
+ *   flags      reserved, must be 0
+ *   horizon    K, 1..PGX_MAX_WHCA_HORIZON
+ *   paths      device i32 [K, batch, agents, 2]: pgx_pibt_plan's / pgx_whca_plan's path_xy layout.  Must not be NULL.
+ *   replan     device u8 [batch, agents], non-zero: replan this agent.  NULL: only agents whose path is no walk.
+ *   priority   device i32 [batch, agents]; NULL: every priority is 0 (index order)
+ *   actions    device [K, batch, agents] of action_dtype.  Must not be NULL.  A kept agent: the action from cell h to
+ *              cell h + 1 up to its last step, 0 afterwards; the others as by pgx_whca_plan.
+ *   path_xy    device i32 [K, batch, agents, 2], as pgx_whca_plan's.  May be NULL, and may be `paths` itself: a workgroup
+ *              reads every `paths` row of its env before it stores anything.  Any other overlap of an output with
+ *              `paths` or `replan` is undefined.
+ *   arrival    device i32 [batch, agents]: pgx_whca_plan's rule on the output cells.  May be NULL.
+ *   failed     device i32 [batch, agents]: 1 for a replanned agent whose search ran empty, else 0.  May be NULL.
+ *   replanned  device i32 [batch, agents]: 1 for every replanned agent -- asked for, or its given path was no walk --
+ *              else 0.  May be NULL.
+ * With replan all ones the first four outputs are pgx_whca_plan's.  From a state with the planned agents on distinct
+ * cells: where the kept agents are free of conflicts among themselves (an agent that arrived under PGX_ON_TARGET_FINISH
+ * takes no part afterwards) and no agent failed, no two planned agents meet in a cell or swap cells at any step, and
+ * what pgx_whca_plan says about pgx_rollout holds.  Cache, allocation, capture (ONE refresh per call, then one more
+ * launch), LDS (pgx_whca_plan's formula), status codes and the order of the checks are pgx_whca_plan's; `paths` NULL or
+ * misaligned is PGX_E_INVALID too. */
+int pgx_repair_plan(pgx_env* env, int32_t flags, int32_t horizon, const int32_t* paths, const uint8_t* replan,
+                    const int32_t* priority, void* actions, int32_t action_dtype, int32_t* path_xy, int32_t* arrival,
+                    int32_t* failed, int32_t* replanned, void* stream);
 
 /* Collision shielding (docs/SPEC.md S15): pgx_pibt_actions' planner -- the same planned agents, serving order
  * (-priority, index), priority inheritance, backtracking, outputs and guarantees -- with every agent's candidate cells

@@ -120,7 +120,7 @@ EXPORTED_SYMBOLS = (
     "pgx_goal_directions", "pgx_shield_actions", "pgx_pibt_plan", "pgx_move_outcomes",
     "pgx_policy_input", "pgx_copy_envs", "pgx_global_state", "pgx_global_state_check",
     "pgx_agent_tokens", "pgx_agent_tokens_length", "pgx_goal_paths", "pgx_pibt_swap_actions", "pgx_pibt_swap_plan",
-    "pgx_agent_forecasts", "pgx_blocking", "pgx_path_conflicts", "pgx_whca_plan",
+    "pgx_agent_forecasts", "pgx_blocking", "pgx_path_conflicts", "pgx_whca_plan", "pgx_repair_plan",
 )
 
 
@@ -248,6 +248,8 @@ def load() -> C.CDLL:
     lib.pgx_pibt_swap_plan.restype = C.c_int
     lib.pgx_whca_plan.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.pgx_whca_plan.restype = C.c_int
+    lib.pgx_repair_plan.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.pgx_repair_plan.restype = C.c_int
     lib.pgx_goal_directions.argtypes = [vp, i32, vp, i32, vp]
     lib.pgx_goal_directions.restype = C.c_int
     lib.pgx_shield_actions.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp]

@@ -1092,7 +1092,7 @@ int64_t pgx_cost_to_go_bytes(const pgx_config* cfg) {
 }
 
 // The launch parameters of the handle's distance-field cache (without `out`); allocates and clears the cache on the
-// first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_pibt_swap_plan, pgx_whca_plan, pgx_goal_directions,
+// first call of any entry point that uses it (pgx_cost_to_go, pgx_pibt_actions, pgx_pibt_plan, pgx_pibt_swap_plan, pgx_whca_plan, pgx_repair_plan, pgx_goal_directions,
 // pgx_shield_actions with PGX_SHIELD_TIE_DISTANCE, pgx_policy_input with a direction channel, pgx_agent_tokens, pgx_goal_paths, pgx_agent_forecasts, pgx_blocking).  `who` names that entry point in the error messages.
 static int cost_to_go_cache(pgx_env* e, hipStream_t s, const char* who, pgx::CostToGoParams* out_p) {
     const pgx_config& c = e->cfg;
@@ -1280,6 +1280,55 @@ int pgx_whca_plan(pgx_env* e, int32_t flags, int32_t horizon, const int32_t* pri
     p.arrival = arrival;
     p.failed = failed;
     PGX_HIP(pgx::launch_whca(p, s));
+    return PGX_OK;
+}
+
+// ---- plan repair (docs/SPEC.md S29): chosen agents are replanned around the paths the others keep -------------------
+int pgx_repair_plan(pgx_env* e, int32_t flags, int32_t horizon, const int32_t* paths, const uint8_t* replan,
+                    const int32_t* priority, void* actions, int32_t action_dtype, int32_t* path_xy, int32_t* arrival,
+                    int32_t* failed, int32_t* replanned, void* stream) {
+    static const char who[] = "pgx_repair_plan";
+    // the argument checks come first and need no device
+    if (!paths) return fail_msg(PGX_E_INVALID, "%s: paths is null", who);
+    if (!actions) return fail_msg(PGX_E_INVALID, "%s: actions is null", who);
+    if (const int rc = check_flags(who, flags, 0)) return rc;
+    if (horizon < 1 || horizon > PGX_MAX_WHCA_HORIZON)
+        return fail_msg(PGX_E_INVALID, "%s: horizon %d is outside 1..%d", who, horizon, PGX_MAX_WHCA_HORIZON);
+    if (const int rc = check_action_dtype(who, action_dtype)) return rc;
+    static const size_t action_bytes[3] = {1, 4, 8};
+    if (const int rc = check_aligned(who, "actions", actions, action_bytes[action_dtype])) return rc;
+    if (const int rc = check_aligned(who, "paths", paths, 4)) return rc;
+    if (const int rc = check_aligned(who, "priority", priority, 4)) return rc;
+    if (const int rc = check_aligned(who, "path_xy", path_xy, 4)) return rc;
+    if (const int rc = check_aligned(who, "arrival", arrival, 4)) return rc;
+    if (const int rc = check_aligned(who, "failed", failed, 4)) return rc;
+    if (const int rc = check_aligned(who, "replanned", replanned, 4)) return rc;
+    DeviceGuard guard;
+    if (const int rc = enter(guard, e, who, true)) return rc;
+    // S28's LDS formula, and nothing above it: the engine's largest env at the longest horizon fits one workgroup
+    if (pgx::repair_lds_bytes(e->cfg.num_agents, horizon) > (size_t)160 * 1024)
+        return fail_msg(PGX_E_INVALID, "%s: %d agents at horizon %d need %zu bytes of LDS, more than a workgroup has", who,
+                        e->cfg.num_agents, horizon, pgx::repair_lds_bytes(e->cfg.num_agents, horizon));
+    hipStream_t s = (hipStream_t)stream;
+    pgx::CostToGoParams cp{};
+    if (const int rc = cost_to_go_cache(e, s, who, &cp)) return rc;
+    PGX_HIP(pgx::launch_cost_to_go_refresh(cp, s));    // once: the fields are the heuristic of every agent's search
+    pgx::RepairParams p{};
+    static_cast<pgx::StateView&>(p) = cp;
+    p.action_dtype = action_dtype;
+    p.cell_bytes = cp.cell_bytes;
+    p.horizon = horizon;
+    p.finish = e->cfg.on_target == PGX_ON_TARGET_FINISH ? 1 : 0;
+    p.field = cp.field;
+    p.priority = priority;
+    p.actions = actions;
+    p.path_xy = path_xy;
+    p.arrival = arrival;
+    p.failed = failed;
+    p.paths = paths;
+    p.replan = replan;
+    p.replanned = replanned;
+    PGX_HIP(pgx::launch_repair(p, s));
     return PGX_OK;
 }
 

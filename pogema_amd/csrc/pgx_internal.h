@@ -479,6 +479,15 @@ struct WhcaParams : StateView {
     int32_t* failed;         // [B][A], may be null
 };
 hipError_t launch_whca(const WhcaParams& p, hipStream_t stream);
+// the repair (pgx_whca.hip: the same kernel with its prologue, docs/SPEC.md S29): chosen agents are served around the
+// given paths the others keep
+struct RepairParams : WhcaParams {
+    const int32_t* paths;    // [K][B][A][2] unpadded, any int32; may be `path_xy` itself
+    const uint8_t* replan;   // [B][A], null: nobody is asked for
+    int32_t* replanned;      // [B][A], may be null
+};
+size_t repair_lds_bytes(int A, int K);   // dynamic LDS of one workgroup
+hipError_t launch_repair(const RepairParams& p, hipStream_t stream);
 
 // ---- collision shielding (pgx_shield.hip): the planner over the caller's action scores ------------------------------
 enum { SCORES_F32 = 0, SCORES_F16 = 1, SCORES_BF16 = 2 };  // PGX_SCORES_* (include/pogema_amd.h)

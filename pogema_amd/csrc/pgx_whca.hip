@@ -19,7 +19,16 @@
 // The served agents' cells stay in LDS, [K + 1][A] packed words (step-major: the lanes of a scatter read consecutive
 // words).  LDS = 8 * 64 * (K + 1) + 2560 + 4 * A * (K + 1) + 9 * A bytes: 27.1 KB at 64 agents and K = 31, 155.5 KB at
 // 1024 agents and K = 31 (one workgroup per CU there).  Nothing but the caller's outputs is written.
+//
+// The same kernel with REPAIR set is pgx_repair_plan (docs/SPEC.md S29): a prologue, one lane per agent, scans the
+// caller's `paths` -- in the map, not an obstacle, one of the five moves from the cell before, the `finish` stop -- and
+// enters every kept agent (a planned agent with `replan` 0 whose given path is a walk) into the [K + 1][A] cells with
+// its last step, exactly as if it had been served: the listing rule above (start within 2K) holds for a kept agent
+// because its path is a walk.  The others are ranked and served as ever.  Every `paths` row of the env is in LDS before
+// the first output is stored, so `path_xy` may be the `paths` buffer itself.  No LDS beyond S28's formula: whether an
+// agent is kept, to be served or not planned is the sign of its s_last.
 #include <algorithm>
+#include <type_traits>
 
 #include "pgx_internal.h"
 
@@ -44,8 +53,8 @@ __host__ __device__ inline size_t whca_lds_bytes(int A, int K) {
     return (n + 7) & ~(size_t)7;
 }
 
-template <typename F>
-__global__ void __launch_bounds__(64) whca_kernel(const WhcaParams p) {
+template <typename F, bool REPAIR>
+__global__ void __launch_bounds__(64) whca_kernel(const std::conditional_t<REPAIR, RepairParams, WhcaParams> p) {
     extern __shared__ u64 whca_lds[];
     const int lane = threadIdx.x;
     const int A = p.A, K = p.horizon, H = p.H, W = p.W, r = p.r;
@@ -69,6 +78,35 @@ __global__ void __launch_bounds__(64) whca_kernel(const WhcaParams p) {
         s_last[j] = (p.active[e0 + j] & ACTIVE_BIT) ? WHCA_UNSERVED : WHCA_UNPLANNED;
     }
     for (int q = lane; q < 5 * 64; q += 64) s_M[q] = 0ull;
+    if constexpr (REPAIR) {
+        // the given paths, one agent per lane: a kept agent's cells and last step go where a served agent's would; an
+        // agent that is not planned holds its cell in every row, so that one loop below stores both
+        for (int j = lane; j < A; j += 64) {
+            uint32_t cur = s_cell[j];
+            const bool planned = s_last[j] == WHCA_UNSERVED;
+            bool walk = planned && !(p.replan && p.replan[e0 + j]);
+            const uint32_t wt = p.tgt[e0 + j] - ring;
+            int last = K;
+            for (int h = 1; h <= K; ++h) {
+                if (walk && h <= last) {
+                    const int32_t* g = p.paths + 2 * ((size_t)(h - 1) * row + e0 + j);
+                    const int gr = g[0], gc = g[1];
+                    // the range check comes first: any int32 may stand there
+                    if ((unsigned)gr < (unsigned)H && (unsigned)gc < (unsigned)W) {
+                        const int dr = gr - (int)(cur >> 16), dc = gc - (int)(cur & 0xFFFFu);
+                        const uint32_t word = bm[(size_t)(gr + r) * p.wpr + ((gc + r) >> 5)];
+                        if (abs(dr) + abs(dc) > 1 || ((word >> ((gc + r) & 31)) & 1u)) walk = false;
+                        cur = ((uint32_t)gr << 16) | (uint32_t)gc;
+                        if (p.finish && cur == wt) last = h;
+                    } else {
+                        walk = false;
+                    }
+                }
+                s_cell[(size_t)h * A + j] = cur;
+            }
+            if (walk) s_last[j] = (int8_t)last;
+        }
+    }
     __syncthreads();
 
     // the order of service; an agent that is not planned keeps its cell
@@ -85,20 +123,48 @@ __global__ void __launch_bounds__(64) whca_kernel(const WhcaParams p) {
         if (pl) s_order[rank] = (uint16_t)i;
         n += __popcll(__ballot(pl));
         if (i < A && !pl) {
-            if (p.arrival) p.arrival[e0 + i] = -1;
+            int32_t arrival = -1;
+            if constexpr (REPAIR) {
+                if (s_last[i] >= 0) {         // a kept agent: S28's rule on its cells
+                    const uint32_t wt = p.tgt[e0 + i] - ring;
+                    for (int h = K; h >= 0; --h) arrival = s_cell[(size_t)h * A + i] == wt ? h : arrival;
+                }
+            }
+            if (p.arrival) p.arrival[e0 + i] = arrival;
             if (p.failed) p.failed[e0 + i] = 0;
         }
+        if constexpr (REPAIR) {
+            if (i < A && p.replanned) p.replanned[e0 + i] = pl ? 1 : 0;
+        }
     }
-    for (int q = lane; q < K * A; q += 64) {
-        const int h = q / A, j = q - h * A;
-        if (s_last[j] != WHCA_UNPLANNED) continue;
-        const size_t o = (size_t)h * row + e0 + j;
-        if (p.action_dtype == 0) static_cast<int8_t*>(p.actions)[o] = 0;
-        else if (p.action_dtype == 1) static_cast<int32_t*>(p.actions)[o] = 0;
-        else static_cast<long long*>(p.actions)[o] = 0;
-        if (p.path_xy) {
-            p.path_xy[2 * o] = (int32_t)(s_cell[j] >> 16);
-            p.path_xy[2 * o + 1] = (int32_t)(s_cell[j] & 0xFFFFu);
+    if constexpr (REPAIR) {
+        // the kept agents and the agents that are not planned: their rows of the cells are final
+        for (int q = lane; q < K * A; q += 64) {
+            const int h = q / A, j = q - h * A;
+            if (s_last[j] == WHCA_UNSERVED) continue;
+            const uint32_t here = s_cell[(size_t)h * A + j], next = s_cell[(size_t)(h + 1) * A + j];
+            const int a = whca_action(here, next);
+            const size_t o = (size_t)h * row + e0 + j;
+            if (p.action_dtype == 0) static_cast<int8_t*>(p.actions)[o] = (int8_t)a;
+            else if (p.action_dtype == 1) static_cast<int32_t*>(p.actions)[o] = a;
+            else static_cast<long long*>(p.actions)[o] = a;
+            if (p.path_xy) {
+                p.path_xy[2 * o] = (int32_t)(next >> 16);
+                p.path_xy[2 * o + 1] = (int32_t)(next & 0xFFFFu);
+            }
+        }
+    } else {
+        for (int q = lane; q < K * A; q += 64) {
+            const int h = q / A, j = q - h * A;
+            if (s_last[j] != WHCA_UNPLANNED) continue;
+            const size_t o = (size_t)h * row + e0 + j;
+            if (p.action_dtype == 0) static_cast<int8_t*>(p.actions)[o] = 0;
+            else if (p.action_dtype == 1) static_cast<int32_t*>(p.actions)[o] = 0;
+            else static_cast<long long*>(p.actions)[o] = 0;
+            if (p.path_xy) {
+                p.path_xy[2 * o] = (int32_t)(s_cell[j] >> 16);
+                p.path_xy[2 * o + 1] = (int32_t)(s_cell[j] & 0xFFFFu);
+            }
         }
     }
     __syncthreads();
@@ -290,15 +356,30 @@ __global__ void __launch_bounds__(64) whca_kernel(const WhcaParams p) {
 
 hipError_t launch_whca(const WhcaParams& p, hipStream_t stream) {
     const size_t lds = whca_lds_bytes(p.A, p.horizon);
-    const void* fn = p.cell_bytes == 4 ? reinterpret_cast<const void*>(&whca_kernel<uint32_t>)
-                                       : reinterpret_cast<const void*>(&whca_kernel<uint16_t>);
+    const void* fn = p.cell_bytes == 4 ? reinterpret_cast<const void*>(&whca_kernel<uint32_t, false>)
+                                       : reinterpret_cast<const void*>(&whca_kernel<uint16_t, false>);
     // an attribute of the kernel function, shared by every handle: raise_lds_limit only ever raises it, and only the
     // first call that needs more touches the runtime
     if (const hipError_t err = raise_lds_limit(fn, lds)) return err;
     if (p.cell_bytes == 4)
-        hipLaunchKernelGGL(whca_kernel<uint32_t>, dim3((unsigned)p.batch), dim3(64), lds, stream, p);
+        hipLaunchKernelGGL((whca_kernel<uint32_t, false>), dim3((unsigned)p.batch), dim3(64), lds, stream, p);
     else
-        hipLaunchKernelGGL(whca_kernel<uint16_t>, dim3((unsigned)p.batch), dim3(64), lds, stream, p);
+        hipLaunchKernelGGL((whca_kernel<uint16_t, false>), dim3((unsigned)p.batch), dim3(64), lds, stream, p);
+    return hipGetLastError();
+}
+
+// LDS of the repair: S28's formula, nothing more (the kept agents' cells and last steps lie where a served agent's do)
+size_t repair_lds_bytes(int A, int K) { return whca_lds_bytes(A, K); }
+
+hipError_t launch_repair(const RepairParams& p, hipStream_t stream) {
+    const size_t lds = repair_lds_bytes(p.A, p.horizon);
+    const void* fn = p.cell_bytes == 4 ? reinterpret_cast<const void*>(&whca_kernel<uint32_t, true>)
+                                       : reinterpret_cast<const void*>(&whca_kernel<uint16_t, true>);
+    if (const hipError_t err = raise_lds_limit(fn, lds)) return err;
+    if (p.cell_bytes == 4)
+        hipLaunchKernelGGL((whca_kernel<uint32_t, true>), dim3((unsigned)p.batch), dim3(64), lds, stream, p);
+    else
+        hipLaunchKernelGGL((whca_kernel<uint16_t, true>), dim3((unsigned)p.batch), dim3(64), lds, stream, p);
     return hipGetLastError();
 }
 

@@ -289,6 +289,20 @@ class Pogema:
         actions = vec.whca_plan(horizon, priority=priority)[0]
         return [[int(a) for a in row] for row in actions[:, 0].cpu().numpy()]
 
+    def repair_plan(self, paths, replan=None, priority=None):
+        """A plan repaired (VecPogema.repair_plan), as one list of actions per step for step().  `paths`: nested lists
+        [K][agents][2], the cell after each step; `replan`: one truth value per agent, None = only the agents whose
+        given path cannot be walked are replanned; `priority`: one integer per agent, None = all equal."""
+        import torch
+        vec = self._vec
+        paths = torch.as_tensor(np.asarray(paths, dtype=np.int32)[:, None], device=vec.device).contiguous()
+        if replan is not None:
+            replan = torch.as_tensor(np.asarray(replan, dtype=bool)[None], device=vec.device)
+        if priority is not None:
+            priority = torch.as_tensor(np.asarray(priority, dtype=np.int64)[None], device=vec.device)
+        actions = vec.repair_plan(paths, replan=replan, priority=priority)[0]
+        return [[int(a) for a in row] for row in actions[:, 0].cpu().numpy()]
+
     def shield_actions(self, scores, priority=None):
         """A policy's action scores made jointly collision-free (VecPogema.shield_actions), as a list for step().
         `scores`: array-like [agents, 5], one score per agent and action, higher is better; `priority`: one integer per

@@ -1,5 +1,5 @@
 """VecPogema's read-only queries on the engine state: expert actions, cost-to-go windows, neighbour lists, the
-cooperative planner and its multi-step lookahead, windowed cooperative A*, collision shielding, direction-to-goal planes, path-to-goal planes,
+cooperative planner and its multi-step lookahead, windowed cooperative A*, plan repair, collision shielding, direction-to-goal planes, path-to-goal planes,
 agent forecasts, blocking counts, path conflicts, move outcomes, the policy input, the global state and the agent tokens.  Each is one C-ABI
 call into caller-owned or fresh output tensors; query_output() is the one place an `out` tensor is checked or allocated.
 """
@@ -199,7 +199,7 @@ class QueryMixin:
 
     @property
     def cost_to_go_builds(self) -> int:
-        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), whca_plan(), goal_directions(), goal_paths(), agent_forecasts(), blocking(), agent_tokens() and
+        """Distance fields cost_to_go(), pibt_actions(), pibt_plan(), whca_plan(), repair_plan(), goal_directions(), goal_paths(), agent_forecasts(), blocking(), agent_tokens() and
         shield_actions(tie_break="distance") have built since this env was created (synchronises the stream)."""
         n = self._lib.pgx_cost_to_go_builds(self._handle, self._stream())
         if n < 0:
@@ -358,6 +358,72 @@ class QueryMixin:
                                            actions.data_ptr(), self._ACTION_CODE[actions.dtype], path_xy.data_ptr(),
                                            arrival.data_ptr(), failed.data_ptr(), self._stream()))
         return actions, path_xy, arrival, failed
+
+    def repair_plan(self, paths, replan=None, priority=None, dtype=torch.int64, out=None):
+        """Plan repair (docs/SPEC.md S29): whca_plan() for chosen agents, around the paths the others keep -- the repair
+        step of an LNS-style solver, and a receding-horizon replan of only the agents whose plan went stale.  Computed
+        on the device from the current state, which the call leaves untouched.
+        `paths`: int32 [K, batch, agents, 2] on this device, contiguous -- a plan in pibt_plan()'s / whca_plan()'s
+        path_xy layout (the cell after step h + 1 at index h, unpadded (row, col)); K, 1..MAX_WHCA_HORIZON (31), is the
+        horizon.  The cells may be any int32.  An active agent's given path is a walk when every cell lies inside the
+        map, is no obstacle and is the cell before it or one of its four neighbours, the first one counted from the
+        agent's cell; under on_target="finish" only up to the first step on the agent's target, which is its last step
+        (what `paths` holds afterwards is ignored), else up to K.
+        `replan`: bool / uint8 [batch, agents] on this device, contiguous; None = nobody is asked for.
+        An active agent with replan == 0 whose given path is a walk is kept: all kept agents' cells and moves are reserved
+        first (up to their last step; conflicts among them are not looked for: that is path_conflicts()' job).  Every
+        other active agent is replanned: served by (-priority, index) exactly as whca_plan() serves an agent, against
+        the kept agents and the replanned agents served before it.  Returns
+            (actions [K, batch, agents] of `dtype`: a kept agent walks its given path up to its last step, then 0;
+             path_xy int32 [K, batch, agents, 2]: a kept agent's given cells, its last cell after its last step;
+             arrival int32 [batch, agents]: whca_plan()'s rule on path_xy;
+             failed int32 [batch, agents]: 1 for a replanned agent whose search ran empty, else 0;
+             replanned int32 [batch, agents]: 1 for every replanned agent -- asked for or not a walk -- else 0).
+        With replan all ones the first four are whca_plan(K, priority)'s.  whca_plan()'s own path_xy with its last m
+        agents of the service order replanned under the same priorities gives that plan again; with replan=None it is
+        returned unchanged and nobody is replanned.  From distinct start cells, where the kept agents are free of
+        conflicts among themselves and nobody failed, the result has no vertex and no edge conflict and whca_plan()'s
+        statement about rollout(actions) holds, with its caveats.
+        `priority`: as in pibt_actions().  Shares cost_to_go()'s cache under pibt_actions()' rules, with one refresh per
+        call.  `out=(actions, path_xy, arrival, failed, replanned)`: caller-owned contiguous tensors on this device
+        (actions int8 / int32 / int64, the others int32); out[path_xy] may be `paths` itself (the repair in place), any
+        other overlap of an output with `paths` is refused."""
+        B, A = self.batch, self.num_agents
+        if not isinstance(paths, torch.Tensor) or paths.dtype != torch.int32:
+            raise TypeError(f"paths must be an int32 torch.Tensor, got "
+                            f"{paths.dtype if isinstance(paths, torch.Tensor) else type(paths).__name__}")
+        if (paths.dim() != 4 or tuple(paths.shape[1:]) != (B, A, 2) or not 1 <= paths.shape[0] <= _lib.MAX_WHCA_HORIZON
+                or not paths.is_contiguous() or paths.device != self.device or paths.data_ptr() % 4):
+            raise ValueError(f"paths must be a contiguous int32 tensor of shape (K, {B}, {A}, 2) with K in "
+                             f"1..{_lib.MAX_WHCA_HORIZON} on {self.device}, got shape {tuple(paths.shape)}")
+        K = int(paths.shape[0])
+        if replan is not None:
+            if not isinstance(replan, torch.Tensor) or replan.dtype not in (torch.bool, torch.uint8):
+                raise TypeError(f"replan must be a bool or uint8 torch.Tensor or None, got "
+                                f"{replan.dtype if isinstance(replan, torch.Tensor) else type(replan).__name__}")
+            if tuple(replan.shape) != (B, A) or replan.device != self.device or not replan.is_contiguous():
+                raise ValueError(f"replan must be a contiguous tensor of shape {(B, A)} on {self.device}")
+        priority = self._priority(priority)
+        names = ("actions", "path_xy", "arrival", "failed", "replanned")
+        actions, path_xy, arrival, failed, replanned = _split(out, names)
+        actions = query_output("out[actions]", actions, self._action_dtypes(dtype, actions), (K, B, A), self.device)
+        path_xy = query_output("out[path_xy]", path_xy, torch.int32, (K, B, A, 2), self.device)
+        arrival = query_output("out[arrival]", arrival, torch.int32, (B, A), self.device)
+        failed = query_output("out[failed]", failed, torch.int32, (B, A), self.device)
+        replanned = query_output("out[replanned]", replanned, torch.int32, (B, A), self.device)
+        if out is not None:
+            lo, hi = paths.data_ptr(), paths.data_ptr() + paths.numel() * 4
+            for name, t in zip(names, (actions, path_xy, arrival, failed, replanned)):
+                if name == "path_xy" and t.data_ptr() == lo:      # the same buffer (shape and strides were checked)
+                    continue
+                if t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * t.element_size():
+                    raise ValueError(f"out[{name}] overlaps paths: only out[path_xy] may, as the same tensor")
+        _lib.check(self._lib.pgx_repair_plan(self._handle, 0, K, paths.data_ptr(),
+                                             replan.data_ptr() if replan is not None else None,
+                                             priority.data_ptr() if priority is not None else None, actions.data_ptr(),
+                                             self._ACTION_CODE[actions.dtype], path_xy.data_ptr(), arrival.data_ptr(),
+                                             failed.data_ptr(), replanned.data_ptr(), self._stream()))
+        return actions, path_xy, arrival, failed, replanned
 
     def shield_actions(self, scores, priority=None, tie_break=None, dtype=torch.int64, out=None):
         """Collision shielding (docs/SPEC.md S15): pibt_actions()' planner with every agent's candidate cells ordered by
